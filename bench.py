@@ -18,6 +18,7 @@ MT19937 stream of the parity tests instead (adds ~25 M host RNG draws per pass).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # ... or is launched as one rank of N (RANK / WORLD_SIZE in the env)
     python bench.py --gpus N --corpus config4              # BASELINE config 4: the fixed 64-utterance corpus (942 segments), STRONG scaling
+    python bench.py --gpus 1 --steps K --dump-outputs DIR  # ... and write the audio of the last timed step to DIR/*.npy
 
 value = useful audio samples per second over all ranks = N * K * sum(wave_len) / max-over-ranks(time).
 """
@@ -36,6 +37,28 @@ sys.path.insert(0, ROOT)
 SAMPLE_RATE = 22050
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec (MI355X_MICROARCH.md); measured-achievable 6290 GB/s
 MFMA_F32_PEAK_TF = 157.3    # v_mfma_f32_16x16x4_f32 dense peak (same guide)
+NOISE_SEED = 2024           # every pass re-seeds the sampling-noise generators with it: each step computes the same audio
+DUMP_BYTES = 64 << 20       # --dump-outputs writes at most this much
+
+
+def dump_outputs(outs, lengths, dirname):
+    """--dump-outputs: the waveforms one timed pass returned (`generate_corpus`'s float64 arrays) as DIR/wave_u<index>.npy.  Utterances
+    are taken in a fixed seeded order while they fit in DUMP_BYTES; the one that no longer fits contributes a fixed seeded sample of
+    its samples (sorted positions), the rest nothing.  Every rank computes the same selection and writes the utterances it finished."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES // 8
+    for u in np.random.RandomState(0).permutation(len(lengths)):
+        if left == 0:
+            break
+        take = min(int(lengths[u]), left)
+        left -= take
+        if outs[u] is None:
+            continue
+        w = np.asarray(outs[u], dtype=np.float64)
+        assert w.shape == (lengths[u],), (u, w.shape, lengths[u])
+        if take < w.shape[0]:
+            w = w[np.sort(np.random.RandomState(1 + int(u)).choice(w.shape[0], take, replace=False))]
+        np.save(os.path.join(dirname, f'wave_u{int(u):04d}.npy'), w)
 
 
 def cpu_baseline(sd, mode, frames, target, overlap, budget_s):
@@ -184,7 +207,12 @@ def main():
                     help='LAUNCH-PATH TEST, not a measurement: run the host side (rank spawn, gloo group, sharding, all-gather, '
                          'unfold, the JSON line) on CPU with the loop replaced by FACTORY(state_dict, mode) -> loop_fn; the line '
                          'is marked "dry_host": true and carries no roofline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the waveforms the last timed step returned as DIR/wave_u<index>.npy (float64, '
+                         'at most 64 MB: a fixed seeded selection beyond that); the inputs and the noise seed depend on the arguments only')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)
@@ -248,6 +276,7 @@ def main():
         eng, loop_fn = model._loop_engine(), None
 
     def one_pass():
+        torch.manual_seed(NOISE_SEED)        # host and device generators: the noise, hence the audio, of every pass is the same
         outs = generate_corpus(model, mels, target, overlap, True, seeds, group=group, noise_source=noise_source,
                                finish='own', check=False, loop_fn=loop_fn)
         if eng is not None:
@@ -267,12 +296,17 @@ def main():
     fence()
     loop_ms = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_pass()
+    for i in range(args.steps):
+        outs = one_pass()
+        if i < args.steps - 1:
+            outs = None                      # (only the last step's audio is kept, for --dump-outputs)
         if eng is not None:
             loop_ms.append(eng.last_loop_ms())
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(outs, [(n - 1) * hop for n in frames], args.dump_outputs)
+    outs = None
     main_info = eng.last_run_info() if eng is not None else None
     if group is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)

@@ -204,6 +204,91 @@ def tacotron_decoder_golden(steps=200, wseed=3):
     print('tacotron decoder golden:', mel.shape, lin.shape, attn.shape, 'mel absmax', float(np.abs(mel).max()))
 
 
+def _text_stubs():
+    un = types.ModuleType('unidecode'); un.unidecode = lambda s: s
+    sys.modules.setdefault('unidecode', un)
+    inf = types.ModuleType('inflect'); inf.engine = lambda: types.SimpleNamespace(number_to_words=lambda *a, **k: 'number')
+    sys.modules.setdefault('inflect', inf)
+
+
+def _reference_tacotron():
+    _text_stubs()
+    from models.tacotron import Tacotron
+    from utils.text.symbols import symbols
+    return Tacotron(embed_dims=hp.tts_embed_dims, num_chars=len(symbols), encoder_dims=hp.tts_encoder_dims,
+                    decoder_dims=hp.tts_decoder_dims, n_mels=hp.num_mels, fft_bins=hp.num_mels, postnet_dims=hp.tts_postnet_dims,
+                    encoder_K=hp.tts_encoder_K, lstm_dims=hp.tts_lstm_dims, postnet_K=hp.tts_postnet_K,
+                    num_highways=hp.tts_num_highways, dropout=hp.tts_dropout, stop_threshold=hp.tts_stop_threshold)
+
+
+def tacotron_mirror_golden(wseed=5):
+    """tests/golden/tacotron_mirror.npz (tests/test_tacotron_mirror.py): the reference's own `Tacotron.generate` for
+    `rich_tacotron_state_dict(5)` (tests/helpers.py: random matrices, biases and batch norms) on the first line of sentences.txt --
+    r = 1 for 60 and 800 steps, r = 3 for 30 steps --, and the two outputs of the torch-initialised `torch.manual_seed(3)` Tacotron
+    whose post-net output became the mel of mol_tacotron_800f.npz (`_, m, _ = tts.generate(x)`, gen_tacotron.py:142)."""
+    import json
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    from helpers import rich_tacotron_state_dict
+    _text_stubs()
+    from utils.text import text_to_sequence
+    with open(os.path.join(REF, 'sentences.txt')) as f:
+        line = f.readline().strip()
+    ids = text_to_sequence(line, hp.tts_cleaner_names)
+    shapes = json.load(open(os.path.join(OUT, 'tacotron_shapes.json')))
+    tts = _reference_tacotron()
+    tts.load_state_dict({k: torch.as_tensor(np.array(v)) for k, v in rich_tacotron_state_dict(wseed, shapes).items()}, strict=True)
+    out = dict(line=np.array(line), ids=np.array(ids, np.int32), config=np.array(repr(dict(wseed=wseed, fixture_tts_seed=3))))
+    with torch.no_grad():
+        for tag, r, steps in (('r1_60', 1, 60), ('r1_800', 1, 800), ('r3_30', 3, 30)):
+            tts.r = r
+            mel, lin, attn = tts.generate(ids, steps=steps)
+            out.update({f'mel_{tag}': np.asarray(mel, np.float32), f'linear_{tag}': np.asarray(lin, np.float32),
+                        f'attention_{tag}': np.asarray(attn, np.float32)})
+        torch.manual_seed(3)
+        tts = _reference_tacotron()
+        mel, lin, _ = tts.generate(ids, steps=800)
+    out.update(fixture_mel=np.asarray(mel, np.float32), fixture_linear=np.asarray(lin, np.float32))
+    np.savez_compressed(os.path.join(OUT, 'tacotron_mirror.npz'), **out)
+    print('tacotron mirror golden:', {k: v.shape for k, v in out.items()})
+
+
+def reference_script_golden():
+    """tests/golden/reference_gen_wavernn.npz (tests/test_reference_scripts.py): what the reference's own `gen_wavernn.py` flow
+    (`gen_from_file`, gen_wavernn.py:38-65) produced with the reference class: output file name, waveform handed to the writer and the
+    next three draws of the global generator -- for a checkpoint of `random_state_dict(17)` at step 123456, `random_mel(5, 40)` saved
+    as utt.npy, `torch.manual_seed(4242)`, batched, target 1100, overlap 55."""
+    import tempfile
+    _text_stubs()
+    written = {}
+    lib.output.write_wav = lambda path, x, sr: written.update(path=str(path), x=np.asarray(x))
+    out = {}
+    for mode in ('RAW', 'MOL'):
+        kw = dict(rnn_dims=hp.voc_rnn_dims, fc_dims=hp.voc_fc_dims, bits=hp.bits, pad=hp.voc_pad, upsample_factors=hp.voc_upsample_factors,
+                  feat_dims=hp.num_mels, compute_dims=hp.voc_compute_dims, res_out_dims=hp.voc_res_out_dims, res_blocks=hp.voc_res_blocks,
+                  hop_length=hp.hop_length, sample_rate=hp.sample_rate, mode=mode)
+        with tempfile.TemporaryDirectory() as td:
+            ckpt = os.path.join(td, 'latest_weights.pyt')
+            m = WaveRNN(**kw)
+            m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in random_state_dict(17, mode=mode).items()})
+            m.step += 123456
+            m.save(ckpt)
+            np.save(os.path.join(td, 'utt.npy'), random_mel(5, 40))
+            sys.modules.pop('gen_wavernn', None)
+            import gen_wavernn as G
+            model = G.WaveRNN(**kw)
+            model.load(ckpt)
+            os.makedirs(os.path.join(td, 'out'))
+            torch.manual_seed(4242)
+            G.gen_from_file(model, __import__('pathlib').Path(td) / 'utt.npy', __import__('pathlib').Path(td) / 'out', True, 1100, 55)
+            assert model.training
+            after = torch.empty(3).uniform_(0, 1).numpy()
+        out[f'{mode}_name'] = np.array(os.path.basename(written['path']))
+        out[f'{mode}_wav'] = written['x']
+        out[f'{mode}_after'] = after
+    np.savez_compressed(os.path.join(OUT, 'reference_gen_wavernn.npz'), **out)
+    print('reference script golden:', {k: (v.shape, v.dtype) for k, v in out.items()})
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     rng_kats()
@@ -211,6 +296,10 @@ if __name__ == '__main__':
     only = sys.argv[1:]
     if not only or 'tacotron_decoder_200f' in only:
         tacotron_decoder_golden()
+    if not only or 'tacotron_mirror' in only:
+        tacotron_mirror_golden()
+    if not only or 'reference_gen_wavernn' in only:
+        reference_script_golden()
     for c in CASES:
         if only and c['name'] not in only:
             continue

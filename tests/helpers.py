@@ -177,3 +177,19 @@ def oracle_utterance(mode, wseed, prune, mel_seed, noise_seed, frames, target=11
                        noise=nz if mode == 'RAW' else np.concatenate([nz[0].reshape(T, -1), nz[1].reshape(T, -1)], axis=1))
     res['ref'] = ref
     return res
+
+
+def rich_tacotron_state_dict(seed, shapes):
+    """`random_tacotron_state_dict(seed, shapes)` with every bias and batch-norm vector random too (seeded uniforms; running variances
+    and batch-norm scales in [0.5, 1.5]) -- TEST ONLY: the weights of tests/golden/tacotron_mirror.npz, whose arrays are what the
+    reference's own `Tacotron.generate` returned for them (scripts/make_golden.py), so that bias and batch-norm paths are pinned too."""
+    import torch
+    from wavernn_amd.synthetic import random_tacotron_state_dict
+    sd = random_tacotron_state_dict(seed, shapes)
+    rs = np.random.RandomState(1000 + seed)
+    for key, shape, dtype in shapes:
+        if dtype != 'float32' or len(shape) != 1 or key == 'stop_threshold':
+            continue
+        lo, hi = (0.5, 1.5) if key.endswith('running_var') or (key.endswith('.weight') and 'bnorm' in key) else (-0.1, 0.1)
+        sd[key] = torch.from_numpy(rs.uniform(lo, hi, shape).astype(np.float32))
+    return sd

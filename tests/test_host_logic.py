@@ -316,6 +316,54 @@ def test_bench_self_launches_two_ranks_dry_host(tmp_path):
     assert line['scaling'] == 'strong' and line['n_gpus'] == 1 and '3 utterances' in line['config']['workload']
 
 
+def test_bench_dump_outputs_dry_host(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the float64 waveforms of the last timed step, one file per utterance; every pass re-seeds the
+    noise, so the dump does not depend on --steps / --warmup, and `--steps` is the number of timed steps the line reports."""
+    import json, subprocess, sys
+    from helpers import ROOT
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'tests'), ROOT, os.environ.get('PYTHONPATH', '')]))
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--utterances', '2', '--frames', '30', '--target', '550',
+            '--overlap', '55', '--no-config4-leg', '--dry-host', 'helpers:oracle_loop_fn']
+    dumps = []
+    for steps, warmup in ((1, 0), (2, 1)):
+        d = tmp_path / f's{steps}'
+        r = subprocess.run(base + ['--steps', str(steps), '--warmup', str(warmup), '--dump-outputs', str(d)], env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line['steps'] == steps and line['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['wave_u0000.npy', 'wave_u0001.npy']
+        dumps.append([np.load(d / f) for f in sorted(os.listdir(d))])
+    for a, b in zip(*dumps):
+        assert a.dtype == np.float64 and a.shape == (29 * 275,) and np.abs(a).max() > 0
+        assert np.array_equal(a, b)
+    assert not np.array_equal(dumps[0][0], dumps[0][1])
+    r = subprocess.run(base + ['--steps', '0'], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and '--steps' in r.stderr
+
+
+def test_bench_dump_outputs_stays_under_its_budget(tmp_path, monkeypatch):
+    """More audio than DUMP_BYTES: a fixed seeded selection -- whole utterances, then a sorted sample of the one that no longer fits."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8 * 1000)
+    lengths = [300, 450, 0, 600, 700]                 # (utterance 2, empty, comes first in the seeded order: it must not end the selection)
+    outs = [np.arange(n, dtype=np.float64) + 1e4 * u for u, n in enumerate(lengths)]
+    for d in ('a', 'b'):
+        bench.dump_outputs(outs, lengths, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b')) and files
+    got = {f: np.load(tmp_path / 'a' / f) for f in files}
+    assert sum(a.nbytes for a in got.values()) == 8 * 1000
+    for f, a in got.items():
+        u = int(f[6:10])
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / 'b' / f))
+        assert np.all(np.diff(a) > 0) and np.isin(a, outs[u]).all()
+    assert sum(a.shape[0] == lengths[int(f[6:10])] for f, a in got.items()) >= len(files) - 1
+    assert 'wave_u0002.npy' in files and got['wave_u0002.npy'].shape == (0,)
+
+
 @pytest.mark.parametrize('n', [2, 4, 8])
 def test_bench_default_command_carries_the_config4_leg_dry_host(n):
     """What the driver's SCALE run issues -- `bench.py --gpus N` and nothing else about the corpus -- measures weak scaling of a batch per

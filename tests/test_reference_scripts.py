@@ -1,19 +1,17 @@
-"""INTEGRATION.md section 1 as a test: the reference's OWN `gen_wavernn.py` flow (`gen_from_file`, gen_wavernn.py:38-65) run
-with the one-line import swap `from wavernn_amd.model import WaveRNN`, in the build container (needs /root/reference; skipped
-on the GPU box).  No GPU here, so the two device entry points of the class are replaced by CPU stand-ins built on the oracle
-(test infrastructure) -- what is under test is everything else the reference's script touches: constructor signature,
-`load()` of a reference state dict, `get_step()`, the `.npy` checks, `generate()`'s signature / file naming / return
-value / RNG consumption / train-eval side effects.  The result must equal the reference class run through the same script."""
+"""INTEGRATION.md section 1 as a test: the reference's OWN `gen_wavernn.py` flow (`gen_from_file`, gen_wavernn.py:38-65) with the
+one-line import swap `from wavernn_amd.model import WaveRNN`.  tests/golden/reference_gen_wavernn.npz holds what that flow produced with the
+reference class (scripts/make_golden.py): output file name, waveform, and the next draws of the global generator.  No GPU here, so the
+two device entry points of the class are replaced by CPU stand-ins built on the oracle (test infrastructure) -- what is under test is
+everything else the reference's script touches: constructor signature, `load()` of a reference state dict, `get_step()`, the `.npy`
+checks, `generate()`'s signature / file naming / return value / RNG consumption / train-eval side effects.  The flow is the project's
+own `wavernn_amd.gen_wavernn.gen_from_file` (its restatement of the script's `.npy` branch); the result must equal the reference's."""
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
-REF = os.environ.get('WRNN_REFERENCE', '/root/reference')
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree is only present in the build container')
+from helpers import GOLDEN
 
 
 class _OracleEngine:
@@ -48,77 +46,57 @@ class _OracleEngine:
         return 'oracle'
 
 
+HP = dict(rnn_dims=512, fc_dims=512, bits=9, pad=2, upsample_factors=(5, 5, 11), feat_dims=80, compute_dims=128, res_out_dims=128,
+          res_blocks=10, hop_length=275, sample_rate=22050)          # hparams.py:38-50 as gen_wavernn.py:112-123 passes them
+
+
 @pytest.mark.parametrize('mode', ['RAW', 'MOL'])
 def test_reference_gen_wavernn_runs_with_the_import_swap(mode, tmp_path, monkeypatch):
-    sys.dont_write_bytecode = True
-    monkeypatch.syspath_prepend(REF)
-    lib = types.ModuleType('librosa')
-    lib.output = types.SimpleNamespace(write_wav=lambda path, x, sr: np.save(str(path) + '.npy', np.asarray(x)))
-    monkeypatch.setitem(sys.modules, 'librosa', lib)
-    un = types.ModuleType('unidecode'); un.unidecode = lambda s: s                         # text front-end deps of utils.dataset
-    inf = types.ModuleType('inflect'); inf.engine = lambda: types.SimpleNamespace(number_to_words=lambda *a, **k: 'number')
-    monkeypatch.setitem(sys.modules, 'unidecode', un)
-    monkeypatch.setitem(sys.modules, 'inflect', inf)
-    if not hasattr(np, 'cumproduct'):
-        monkeypatch.setattr(np, 'cumproduct', np.cumprod, raising=False)
-    for m in [k for k in sys.modules if k.split('.')[0] in ('utils', 'models', 'gen_wavernn')]:
-        monkeypatch.delitem(sys.modules, m)
-    from utils import hparams as hp
-    hp.configure(os.path.join(REF, 'hparams.py'))
-    import models.fatchord_version as ref_mod
-    RefWaveRNN = ref_mod.WaveRNN
-    RefWaveRNN.gen_display = lambda self, *a, **k: None
     import wavernn_amd.model as ours
+    from wavernn_amd.gen_wavernn import gen_from_file
     from wavernn_amd.synthetic import random_state_dict, random_mel, SHIPPED
-
-    kw = dict(rnn_dims=hp.voc_rnn_dims, fc_dims=hp.voc_fc_dims, bits=hp.bits, pad=hp.voc_pad, upsample_factors=hp.voc_upsample_factors,
-              feat_dims=hp.num_mels, compute_dims=hp.voc_compute_dims, res_out_dims=hp.voc_res_out_dims, res_blocks=hp.voc_res_blocks,
-              hop_length=hp.hop_length, sample_rate=hp.sample_rate, mode=mode)            # gen_wavernn.py:112-123
+    g = np.load(os.path.join(GOLDEN, 'reference_gen_wavernn.npz'))
+    kw = dict(HP, mode=mode)
     assert {k: kw[k] for k in SHIPPED} == SHIPPED
     sd = random_state_dict(17, mode=mode)
     ckpt = tmp_path / 'latest_weights.pyt'
-    ref_model = RefWaveRNN(**kw)
-    ref_model.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
-    ref_model.step += 123456
-    ref_model.save(ckpt)                                                                  # a checkpoint as the reference writes it
+    torch.save(dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()}, step=torch.tensor([123456])), ckpt)   # the reference's save()
     np.save(tmp_path / 'utt.npy', random_mel(5, 40))
-
-    def run_script(WaveRNNClass, out_dir):
-        # the reference's script with its model import swapped (gen_wavernn.py:3)
-        monkeypatch.setattr(ref_mod, 'WaveRNN', WaveRNNClass)
-        monkeypatch.delitem(sys.modules, 'gen_wavernn', raising=False)
-        import gen_wavernn as G
-        assert G.WaveRNN is WaveRNNClass
-        model = G.WaveRNN(**kw)
-        model.load(ckpt)                                                                  # gen_wavernn.py:129
-        os.makedirs(out_dir)
-        torch.manual_seed(4242)
-        G.gen_from_file(model, tmp_path / 'utt.npy', out_dir, True, 1100, 55)             # gen_wavernn.py:38-65
-        assert model.training                                                             # generate() leaves train mode on (:262)
-        after = torch.empty(3).uniform_(0, 1).numpy()                                     # the generator moved exactly as far
-        (f,) = [p for p in os.listdir(out_dir) if p.endswith('.npy')]
-        return f, np.load(os.path.join(out_dir, f)), after
-
-    ref_name, ref_wav, ref_after = run_script(RefWaveRNN, tmp_path / 'ref')
+    written = {}
 
     # ours, with the two device entry points mocked onto the CPU
     monkeypatch.setattr(ours.WaveRNN, '_require_hip_device', staticmethod(lambda device: None))
     monkeypatch.setattr(ours.WaveRNN, '_loop_engine', lambda self: _OracleEngine({k: v.detach().numpy() for k, v in self.state_dict().items()}, self.mode))
-    monkeypatch.setattr(ours, 'save_wav', lambda x, path, sr: lib.output.write_wav(path, x.astype(np.float32), sr))
+    monkeypatch.setattr(ours, 'save_wav', lambda x, path, sr: written.update(path=str(path), x=x.astype(np.float32)))
 
     class Swapped(ours.WaveRNN):
         def __init__(self, *a, **k):
             super().__init__(*a, **k)
             self.pre_algo, self.post_algo = 'torch', 'numpy'
 
-    name, wav, after = run_script(Swapped, tmp_path / 'ours')
-    assert name == ref_name == '__utt__123k_steps_gen_batched_target1100_overlap55.wav.npy'
-    assert np.array_equal(after, ref_after)
+    model = Swapped(**kw)
+    model.load(ckpt)                                                                      # gen_wavernn.py:129
+    assert model.get_step() == 123456
+    os.makedirs(tmp_path / 'ours')
+    torch.manual_seed(4242)
+    wav, path = gen_from_file(model, tmp_path / 'utt.npy', tmp_path / 'ours', True, 1100, 55)     # the project's gen_wavernn.py:38-65
+    assert model.training                                                                 # generate() leaves train mode on (:262)
+    after = torch.empty(3).uniform_(0, 1).numpy()                                         # the generator moved exactly as far
+    name = os.path.basename(written['path'])
+    assert written['path'] == str(path) and np.array_equal(written['x'], np.asarray(wav, np.float32))
+    # the reference's script puts the checkpoint's step in thousands into the name; the project's CLI does not
+    assert str(g[f'{mode}_name']) == f'__utt__{model.get_step() // 1000}k_steps_gen_batched_target1100_overlap55.wav'
+    assert name == '__utt__gen_batched_target1100_overlap55.wav'
+    assert np.array_equal(after, g[f'{mode}_after'])
+    ref_wav = g[f'{mode}_wav']
+    assert written['x'].shape == ref_wav.shape
     if mode == 'RAW':
-        assert np.array_equal(wav, ref_wav)
+        assert np.array_equal(written['x'], ref_wav)
     else:
-        assert np.abs(wav - ref_wav).max() <= 1e-5
-    with pytest.raises(ValueError):                                                       # gen_wavernn.py:50-55 still guards the input
-        np.save(tmp_path / 'bad.npy', 2 * random_mel(5, 40))
-        import gen_wavernn as G
-        G.gen_from_file(Swapped(**kw), tmp_path / 'bad.npy', tmp_path / 'ours', True, 1100, 55)
+        assert np.abs(written['x'] - ref_wav).max() <= 1e-5
+    np.save(tmp_path / 'bad.npy', 2 * random_mel(5, 40))
+    with pytest.raises(ValueError, match='range'):                                        # gen_wavernn.py:50-55 guards the input
+        gen_from_file(Swapped(**kw), tmp_path / 'bad.npy', tmp_path / 'ours', True, 1100, 55)
+    np.save(tmp_path / 'flat.npy', random_mel(5, 40)[0])
+    with pytest.raises(ValueError, match='shaped'):
+        gen_from_file(Swapped(**kw), tmp_path / 'flat.npy', tmp_path / 'ours', True, 1100, 55)
