@@ -44,7 +44,8 @@ enum { WRNN_MODE_RAW = 0, WRNN_MODE_MOL = 1 };  /* reference: WaveRNN(mode='RAW'
 
 /* Loop kernel selection. */
 enum {
-    WRNN_ALGO_AUTO = 0,     /* shipped dims: WRNN_ALGO_SPARSE when the pack qualifies (wrnn_pack_sparse_blocks() > 0) on a 256-CU device, else
+    WRNN_ALGO_AUTO = 0,     /* shipped dims: WRNN_ALGO_SPARSE when a MOL pack qualifies (wrnn_pack_sparse_blocks() > 0) on a 256-CU device (a qualifying
+                               9-bit RAW pack keeps the dense kernels: WRNN_ALGO_SPARSE runs it on request), else
                                WRNN_ALGO_CHAIN (MOL or RAW with 512 classes, <= 128 segments, 256 CUs, dense pack), else WRNN_ALGO_DUO (MOL, or RAW
                                with 512 classes; >= 128 CUs),
                                else WRNN_ALGO_STREAM; other dims: wrnn_generic_kernel */
@@ -64,7 +65,8 @@ enum {
                                waves (W_ih and W_hh of the CU's 16 units in registers, the fc tile in LDS: operand by LDS-DMA, MFMA block, partial tiles)
                                and four service waves (partial sums, GRU cell, publishes, conditioning, fc3 + sampling) that meet through LDS counters;
                                gh never leaves the CU.  Same split, workspace, exchange buffer and state layout as WRNN_ALGO_DUO (csrc/wrnn_octo.hip) */
-    WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL; BASELINE config 5): needs GRU matrices whose 16x1 block rows keep <= 64 columns
+    WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
+                               four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
                                (wrnn_pack_sparse_blocks) and a 256-CU device; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
                                step is the latency of one chain, sixteen chains run side by side (csrc/wrnn_sparse.hip) */
 };
@@ -153,7 +155,8 @@ typedef struct wrnn_options {
                                   through (no XCD-local plain stores), bit 14 = with phase_clocks: the stage time line of three steps as well
                                   (phase_clocks then holds [256 * 32 + 512 * 512] words; scripts/gpu_duo_trace.py);
                                 wrnn_sparse_kernel, wrnn_chain_kernel: bits 2, 8 as wrnn_duo_kernel; wrnn_sparse_kernel: bit 11 = the DENSE fc stages on a pack whose
-                                  Linear layers are block-sparse too; wrnn_chain_kernel: bit 5 = MoL's fc3 tiles read from LDS (round 5).
+                                  Linear layers are block-sparse too, bit 4 = MOL with gathered fc stages: y2 published and fc3 run densely by the sampling
+                                  workgroup instead of folded into the fc2 tiles (RAW: no effect -- y2 is always published); wrnn_chain_kernel: bit 5 = MoL's fc3 tiles read from LDS (round 5).
                                 When the two-workgroups-per-CU grid of wrnn_duo_kernel is refused the call returns WRNN_ERR_RESIDENCY; the
                                 caller may run it again with WRNN_ALGO_LOOP (another workspace layout: query its size) or _STREAM. */
     const float *force_x;    /* test hook, device [n,T]: value fed back as x_t instead of the sample (teacher forcing) */
@@ -198,7 +201,7 @@ void wrnn_pack_destroy(wrnn_pack *p);
 /* bytes of loop weights the reference streams per step (the W of SURVEY.md section 8d) */
 size_t wrnn_pack_weight_bytes(const wrnn_pack *p);
 /* block sparsity of the pack's GRU matrices: the largest number of non-zero 16x1 blocks in any (matrix, gate, 16-row) block
- * row -- positive when WRNN_ALGO_SPARSE can run this pack (<= 64, MOL), negated when it cannot */
+ * row -- positive when WRNN_ALGO_SPARSE can run this pack (<= 64; MOL, or RAW with 512 classes), negated when it cannot */
 int wrnn_pack_sparse_blocks(const wrnn_pack *p);
 /* (v9) the same figure for fc1 / fc2 (their first H columns; 32 block rows of 16 each): positive when the Linear layers are block-sparse
  * too -- the reference's pruning recipe prunes them with the GRUs, notebooks/"Pruning - Scratchpad.ipynb":199-204 -- and

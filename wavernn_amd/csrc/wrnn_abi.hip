@@ -29,7 +29,7 @@ int duo_clusters(int n_cus);
 int duo_max_depth();
 size_t duo_xbuf_bytes(int G);
 size_t duo_xbuf_bytes_max();
-hipError_t launch_sparse(const LoopArgs &args, int nbp, hipStream_t stream);
+hipError_t launch_sparse(const LoopArgs &args, int nbp, int mode, hipStream_t stream);
 int sparse_clusters(int n_cus);
 size_t sparse_state_floats();
 size_t sparse_xbuf_bytes();
@@ -229,7 +229,7 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         }
     }
     // ---- block-sparse view of the GRU matrices (16x1 blocks: 16 consecutive rows of one gate x 1 column) -----------
-    // usable by wrnn_sparse_kernel when every block row keeps <= 64 columns (~5 % density keeps ~26 +- 5)
+    // usable by wrnn_sparse_kernel when every block row keeps <= 64 columns (~5 % density keeps ~26 +- 5), for MOL and for 9-bit RAW (512 classes)
     int sp_nbp = 0, sp_max = 0, sp_fc_max = 0;
     bool sp_fc_ok = false;
     size_t o_spv = 0, o_spc = 0, o_sfv = 0, o_sfc = 0;
@@ -263,7 +263,7 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
                 }
                 if ((int)cv.size() > sp_fc_max) sp_fc_max = (int)cv.size();
             }
-        if (sp_max <= 64 && w->mode == WRNN_MODE_MOL) {
+        if (sp_max <= 64 && (w->mode == WRNN_MODE_MOL || C == H)) {
             sp_nbp = sp_max <= 48 ? 48 : 64;
             if (sp_fc_max <= 64) {                        // one NBP for the gate and the fc tiles of a launch
                 if (sp_fc_max > 48) sp_nbp = 64;
@@ -465,7 +465,7 @@ const wrnn_options *norm_options(const wrnn_options *opt, wrnn_options *tmp)
 }
 
 // kernel choice: the block-sparse kernel if the pack qualifies (MOL, every 16-row block row of the GRU matrices keeps <= 64 columns) on a
-// 256-CU device, else the two-workgroups-per-CU loop kernel (RAW with 512 classes or MOL, >= 128 CUs), else the one-per-CU loop kernel,
+// 256-CU device (a qualifying 9-bit RAW pack runs on it on request only: algo = sparse), else the two-workgroups-per-CU loop kernel (RAW with 512 classes or MOL, >= 128 CUs), else the one-per-CU loop kernel,
 // else stream
 int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
 {
@@ -500,7 +500,8 @@ int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
         set_err("wrnn_chain_kernel needs MOL or RAW with 512 classes, and >= 256 CUs (C = %d, device: %d CUs)", p->C, p->n_cus);
         return !shape_ok ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
     }
-    if (algo == WRNN_ALGO_CHAIN || (algo == WRNN_ALGO_AUTO && chain_hw && groups <= CHAIN_AUTO_GROUPS && !p->sp_nbp)) {
+    const bool sparse_auto = p->sp_nbp && p->mode == WRNN_MODE_MOL;      // (RAW: the sparse kernel's summation order is not the oracle's -- `auto` keeps the dense kernels)
+    if (algo == WRNN_ALGO_CHAIN || (algo == WRNN_ALGO_AUTO && chain_hw && groups <= CHAIN_AUTO_GROUPS && !sparse_auto)) {
         const int gmax = chain_max_depth();
         int g = o->depth;
         if (g < 1 || g > gmax) {
@@ -525,16 +526,16 @@ int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
         pl->tab_fps = DUO_TAB_FPS;
     }
     // a block-sparse pack runs on wrnn_sparse_kernel (round 5: 16 clusters of 16 CUs, one group of 16 segments each -- the step is the
-    // latency of one chain, and sixteen chains run side by side): `auto` picks it whenever the pack and the device qualify
+    // latency of one chain, and sixteen chains run side by side): `auto` picks it whenever a MOL pack and the device qualify
     const int scl = sparse_clusters(p->n_cus);
     if (algo == WRNN_ALGO_SPARSE && (!p->sp_nbp || scl < 1)) {
-        set_err("block-sparse kernel needs MOL, >= 256 CUs and GRU matrices with <= 64 surviving 16x1 blocks per block row "
-                "(this pack: up to %d; device: %d CUs)", p->sp_max_blocks, p->n_cus);
+        set_err("block-sparse kernel needs MOL or RAW with 512 classes, >= 256 CUs and GRU matrices with <= 64 surviving 16x1 blocks per block row "
+                "(this pack: mode %s, %d classes, up to %d blocks; device: %d CUs)", p->mode == WRNN_MODE_MOL ? "MOL" : "RAW", p->C, p->sp_max_blocks, p->n_cus);
         return (!p->sp_nbp) ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
     }
     if (pl->kind == K_CHAIN) {
         // (planned above)
-    } else if (algo == WRNN_ALGO_SPARSE || (algo == WRNN_ALGO_AUTO && p->sp_nbp && scl >= 1)) {
+    } else if (algo == WRNN_ALGO_SPARSE || (algo == WRNN_ALGO_AUTO && sparse_auto && scl >= 1)) {
         pl->kind = K_SPARSE; pl->ncl = scl; pl->G = 1;
         pl->rounds = (groups + scl - 1) / scl;
         pl->per_round = (B + pl->rounds - 1) / pl->rounds;
@@ -542,7 +543,7 @@ int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
         if (pl->ngr_max > scl) { pl->rounds += 1; pl->per_round = (B + pl->rounds - 1) / pl->rounds; pl->ngr_max = (pl->per_round + SEG - 1) / SEG; }
         int slab = o->slab_steps;
         if (slab < 1) {
-            slab = (int)((32u << 20) / ((size_t)pl->per_round * 11 * sizeof(float) * pl->rounds));      // one slab of derived noise
+            slab = p->mode == WRNN_MODE_MOL ? (int)((32u << 20) / ((size_t)pl->per_round * 11 * sizeof(float) * pl->rounds)) : 4096;      // one slab of derived MOL noise
             if (slab < 16) slab = 16;
             if (slab > 4096) slab = 4096;
         }
@@ -901,7 +902,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
                 a.t0 = s0; a.t1 = s1; a.cI_t0 = s0; a.rb0 = rb0; a.Btot = nr; a.NG = ngr; a.resume = s0 > 0 ? 1 : 0;
                 a.kind_tag = chain ? 4 : sparse ? 3 : (duo ? (octo ? 5 : 2) : 1);
                 if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-                hipError_t e = chain ? launch_chain(a, p->mode, stream) : sparse ? launch_sparse(a, p->sp_nbp, stream) : (duo ? (octo ? launch_octo(a, pl.ncl, p->mode, stream) : launch_duo(a, pl.ncl, p->mode, stream)) : launch_loop(a, pl.ncl, p->mode, stream));
+                hipError_t e = chain ? launch_chain(a, p->mode, stream) : sparse ? launch_sparse(a, p->sp_nbp, p->mode, stream) : (duo ? (octo ? launch_octo(a, pl.ncl, p->mode, stream) : launch_duo(a, pl.ncl, p->mode, stream)) : launch_loop(a, pl.ncl, p->mode, stream));
                 // (two workgroups per CU not co-resident right now: WRNN_ERR_RESIDENCY -- the caller re-plans with WRNN_ALGO_LOOP, whose
                 // workspace layout is another one: wavernn_amd/engine.py does)
                 if (e != hipSuccess) {

@@ -1,4 +1,4 @@
-// wrnn_sparse.hip -- persistent WaveRNN loop kernel for BLOCK-SPARSE GRU weights (MOL) on MI355X (gfx950 / CDNA4); round 5 rebuild.
+// wrnn_sparse.hip -- persistent WaveRNN loop kernel for BLOCK-SPARSE GRU weights (MOL; and 9-bit RAW on request) on MI355X (gfx950 / CDNA4); round 5 rebuild.
 //
 // BASELINE config 5: the four GRU matrices pruned per gate to ~5 % density in 16x1 blocks (wavernn_amd/prune.py: the rule of the
 // reference's "Pruning - Scratchpad" notebook, JSON :40-186, applied to block magnitudes); the loop it runs is the reference's
@@ -38,9 +38,14 @@
 //     depends on neither T nor the corpus.
 // Skipping exact zeros changes no partial sum; the summation ORDER differs from the dense kernels (surviving columns ascending, four
 // at a time), so parity is to the MoL tolerance (tests/test_gpu_parity.py, tests/test_gpu_fullsize.py).
+// 9-bit RAW (MODE 0, every difference behind `if constexpr`: the MOL instantiations are the code they were): fc2 publishes y2, fc3 (512 x 512) is a dense
+// stage of EVERY workgroup -- its 32 rows, the non-FCS fc stage's shape with the A operand in LDS -- published as layer 16 (sentinel, re-armed two ahead),
+// and rnn2's workgroups 0, 5, 6, 7 sample, one segment per wave (wrnn_raw.h); class indices against the oracle: tests/test_gpu_sparse_raw.py, exchange
+// rules: tests/test_sparse_raw_exchange_model.py.
 #include <type_traits>
 
 #include "wrnn_ring.h"
+#include "wrnn_raw.h"
 
 namespace wrnn {
 
@@ -53,9 +58,9 @@ static_assert(SPCLUSTERS <= LMAXG * MAXCL, "one exchange-buffer region per clust
 static_assert(SPCLUSTERS * SPWG <= XCC_WORDS, "placement table");
 
 struct SpLds {
-    int off_seg, off_part, off_log, off_misc, off_prof, off_ct1, off_f3, total;
+    int off_seg, off_part, off_log, off_misc, off_prof, off_ct1, off_f3, off_lgt, total;
 };
-__host__ __device__ inline SpLds sp_lds()
+__host__ __device__ inline SpLds sp_lds(bool raw = false)
 {
     SpLds l;
     int o = 0;
@@ -66,7 +71,8 @@ __host__ __device__ inline SpLds sp_lds()
     l.off_prof = o; o += 64;                 // [32] u64 phase clocks (profiling builds)
     o = (o + 3) & ~3;
     l.off_ct1 = o;  o += 5 * 64 * (CK + 4);   // rnn2's cI-forming workgroups: the I-layer tiles [wave 0..3 | wave 0's SECOND block][kk | bias][lane]
-    l.off_f3 = o;   o += 2 * XT;             // the sampling workgroup: fc3 (30 x 512 = two 16-row tiles) in A-fragment order
+    l.off_f3 = o;   o += 2 * XT;             // the sampling workgroup: fc3 (30 x 512 = two 16-row tiles) in A-fragment order; RAW: every workgroup's 32 rows of fc3
+    l.off_lgt = o;  if (raw) o += SEG * LDC;  // RAW, the sampling workgroups: the gathered logits [segment][class], stride LDC
     l.total = o;
     return l;
 }
@@ -188,13 +194,16 @@ __device__ __forceinline__ void mfma2(const float (&a0)[AF], const float (&a1)[A
 // PROF (wrnn_options.phase_clocks; thread 0 of every workgroup, shader clocks per segment of a step, in program order): rnn1: 0 drain + wait for
 // x_{t-1}, 1 cell + publish, 2 wait for h1(t), 3 gh tiles, 4 wait x2, 5 fc1, 6 wait y1, 7 fc2, 8 wait cI(t+1), 9 W_ih . cI tiles;
 // rnn2: 0 drain + wait for x1(t), 1 gate tiles + cell + publish, 2 wait x2, 3 fc1, 6 wait y1, 7 fc2, 8 wait y2, 9 fc3 + sampling, 4 wait h2 (there), 5 gh
-// tiles, 10 cI(t+2) formed; 15 = steps
-template <int NBP, bool FCS, bool LA, bool PROF>
+// tiles, 10 cI(t+2) formed; 15 = steps.  RAW (MODE 0), every workgroup: 11 wait y2, 12 fc3 -> logits; the sampling workgroups: 13 wait logits, 14 sampling
+// (9-bit RAW: fc3 is a dense 512 x 512 stage of every workgroup -- 32 rows each, K split over the 4 waves, A in LDS -- published as layer 16, and FOUR
+// rnn2 workgroups sample, one segment per wave: see the kernel's comment)
+template <int NBP, bool FCS, int MODE, bool LA, bool PROF>
 __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const int rg, const int gid, const int ub, const int wgi, const bool loc)
 {
     constexpr int MPW = NBP / 4;
-    const SpLds L = sp_lds();
-    float *PART = smem + L.off_part, *fc3b = smem + L.off_log, *F3 = smem + L.off_f3;
+    constexpr bool MOL = MODE == 1;
+    const SpLds L = sp_lds(!MOL);
+    float *PART = smem + L.off_part, *fc3b = smem + L.off_log, *F3 = smem + L.off_f3, *LGT = smem + L.off_lgt;
     int *SEGT = reinterpret_cast<int *>(smem + L.off_seg);
     u64 *PROFL = reinterpret_cast<u64 *>(smem + L.off_prof);
     u64 plast = 0;
@@ -212,7 +221,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     const int mshift = a.hop_shift;
     const int zrow = a.Nall * a.tab_fps;
     float *const outp = a.out, *const dbgl = a.dbg_logits;
-    const float *const forcex = a.force_x, *const noise_pre = a.noise_pre;
+    const float *const forcex = a.force_x, *const noise_pre = a.noise_pre, *const noise_raw = a.noise;
     const float *const mels_up = a.mels_up, *const aux_fr = a.aux_fr, *const mel_coef = a.mel_coef;
     const int mel_stage = a.mel_stage;
     const int NR = a.Btot, NGR = a.NG;
@@ -220,7 +229,10 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     const int b0g = a.rb0 + b0;                         // first segment of the group in the call
     constexpr int L_H = LA ? 0 : 1, L_XR = LA ? 5 : 6, L_IN = LA ? 4 : 5;
     float *const state_wg = a.state + (size_t)gid * SPSTATE_CL + (size_t)wgi * SPSTATE_WG;
-    const bool sampler = !LA && ub == 0;
+    // MOL: rnn2's workgroup 0 samples.  RAW: rnn2's workgroups 0, 5, 6, 7 -- sampler sidx = 0 .. 3, wave w: segment 4 sidx + w -- the rnn2 workgroups with
+    // the least to do behind fc3 (0 forms no cI; 5-7 one block per wave, 1-4 a second one on wave 0): a sampler's gh stage and cI block follow its sampling
+    const bool sampler = !LA && (ub == 0 || (!MOL && ub >= 5));
+    const int sidx = ub == 0 ? 0 : ub - 4;
 
     // ---- weights: the wave's gate tiles of W_ih and W_hh, the workgroup's two fc1 and two fc2 tiles
     GateTiles<MPW> gi, gh;
@@ -239,18 +251,30 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     // FCS: fc3 FOLDED into the fc2 tiles (as wrnn_chain.hip, round 6): a wave that owns an fc2 row block multiplies ITS 16 rows of y2 through fc3's columns of
     // those rows -- two 16-row tiles x 4 MFMAs; K-slot kq of MFMA e <-> row 4 kq + e, i.e. the B operand IS the lane's accumulator element e: no data moves --
     // and publishes two partial logit tiles (layers 3 and 16) instead of y2; the sampling workgroup adds the 32 waves' tiles instead of running 64 MFMAs per wave.
-    const bool fold3 = FCS && (a.tuning & 16) == 0;     // (A/B: tuning bit 4 = y2 published, dense fc3 on the sampling workgroup)
+    const bool fold3 = MOL && FCS && (a.tuning & 16) == 0;     // (A/B: tuning bit 4 = y2 published, dense fc3 on the sampling workgroup; RAW: always published)
     float A3[2][4];
-    if constexpr (FCS) {
+    if constexpr (FCS && MOL) {
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) A3[q][e] = (16 * q + fi < C) ? a.fc3_w[(size_t)(16 * q + fi) * H + LU * (2 * wgi + (w & 1)) + 4 * kq + e] : 0.f;
     }
     for (int q = tid; q < L.off_f3; q += NT) smem[q] = 0.f;
-    if (sampler) {                                      // fc3 -> LDS (fragment order as in the pack)
-        for (int q = tid; q < 2 * XT / 4; q += NT) reinterpret_cast<float4 *>(F3)[q] = reinterpret_cast<const float4 *>(a.fc3f)[q];
+    if constexpr (MOL) {
+        if (sampler) {                                  // fc3 -> LDS (fragment order as in the pack)
+            for (int q = tid; q < 2 * XT / 4; q += NT) reinterpret_cast<float4 *>(F3)[q] = reinterpret_cast<const float4 *>(a.fc3f)[q];
+        }
+    } else {
+        // RAW: this workgroup's fc3 rows [32 wgi, 32 wgi + 32) -> LDS as two 16-row A tiles in fragment order ([tile][wave][k-block r][lane][4] =
+        // fc3_w[32 wgi + 16 tile + fi][128 wave + 16 r + 4 kq + e], the MOL pack's fc3f layout) -- the 64 KB region the MOL sampler's fc3 takes
+        for (int q = tid; q < 2 * XT / 4; q += NT) {
+            const int l6 = q & 63, r = (q >> 6) & 7, wv = (q >> 9) & 3, tile = q >> 11;
+            const float *src = a.fc3_w + (size_t)(32 * wgi + 16 * tile + (l6 & 15)) * H + 128 * wv + 16 * r + 4 * (l6 >> 4);
+            reinterpret_cast<float4 *>(F3)[q] = make_float4(src[0], src[1], src[2], src[3]);
+        }
     }
+    float b3r[2] = {0.f, 0.f};                          // RAW: fc3.bias of the thread's logit rows 32 wgi + pu, 32 wgi + 16 + pu
+    if constexpr (!MOL) { b3r[0] = a.fc3_b[32 * wgi + pu]; b3r[1] = a.fc3_b[32 * wgi + 16 + pu]; }
     // constants of the gate pointwise role (units u0 + e): rnn1: b_ih1, u1 = W_ih1 . w0 (the x_{t-1} term), w0 (rnn2's b_ih2 is inside c2f); b_hh
     float cb[3][4], ux[3][4], w0o[4], bh[3][4];
 #pragma unroll
@@ -274,7 +298,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     // workgroups -- fc1 / fc2 are on the chain -- ran ~0.3 us slower, profiles/r05e_sparse_phase_clocks.json)
     float *CT0 = smem + L.off_ct1 + w * 64 * (CK + 4), *CT1 = smem + L.off_ct1 + 4 * 64 * (CK + 4);
     __syncthreads();
-    if (sampler && tid >= 32 && tid < 64) fc3b[tid - 32] = tid - 32 < 30 ? a.fc3_b[tid - 32] : 0.f;
+    if (MOL && sampler && tid >= 32 && tid < 64) fc3b[tid - 32] = tid - 32 < 30 ? a.fc3_b[tid - 32] : 0.f;
     if (cond_wg) {
         CondTile c1;
         cond_tile_init(c1, a.I_cT, a.I_b, cblk0, lane);
@@ -468,7 +492,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         u32x4 qx, qh;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            h[e] = gru_update_fast(gir[e], giz[e], gin[e], ghr[e], ghz[e], ghn[e], h[e]);
+            if constexpr (MOL) h[e] = gru_update_fast(gir[e], giz[e], gin[e], ghr[e], ghz[e], ghn[e], h[e]);
+            else h[e] = gru_update(gir[e], giz[e], gin[e], ghr[e], ghz[e], ghn[e], h[e]);      // RAW (class indices): the library forms, as the dense RAW kernels
             qx[e] = __float_as_uint(xin[e] + h[e]);       // x1 = xi + h1 (:212) / x2 = x1 + h2 (:216)
             qh[e] = __float_as_uint(h[e]);
         }
@@ -670,6 +695,80 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         pp ^= 1;
         SPX(9);
     };
+    // RAW, every workgroup: logits(t) = fc3(y2(t)) + b of rows [32 wgi, 32 wgi + 32) (:223) -- the dense fc stage's shape: K split over the 4 waves (wave w:
+    // y2 rows 128 w .. 128 w + 127), 2 x 32 MFMAs per wave with A from LDS, partial tiles through LDS, one barrier, the bias -> layer 16 (fragment order),
+    // then the wave's re-arm of its quarter of the workgroup's two layer-16 blocks in entry (t + 2) % 4: behind its workgroup's poll of y2(t) of every
+    // workgroup (the barrier), which needed every sampler past its sampling of step t - 1 (tests/test_sparse_raw_exchange_model.py)
+    auto fc3_raw = [&]() {
+        const int sb = cbase + (t & (DRING - 1)) * XTB;
+        u32x4 x[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, sb + 3 * DLAYERB, 16 /* sc1 */);
+        if (__builtin_expect(!frag_there(x, live), 0))
+            wait_for([&] { return frag_there(x, live); },
+                     [&] {
+#pragma unroll
+                         for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, sb + 3 * DLAYERB, 16 /* sc1 */);
+                     },
+                     status, dead, 0x703u, t);
+        SPX(11);
+        float b[32];
+        frag_to_b(x, b);
+        float *PW = PART + pp * (NW * 2 * 256);
+        put_partial<2>(PW, w, 0, lane, mfma1_lds(F3 + frag_off(w, 0, lane), b));
+        put_partial<2>(PW, w, 1, lane, mfma1_lds(F3 + XT + frag_off(w, 0, lane), b));
+        lds_barrier();
+        publish4l(xrs, sb + 16 * DLAYERB + (2 * wgi) * 1024, tid, get_partial<2>(PW, 0, pu, pj) + b3r[0], pj < nb, loc);
+        publish4l(xrs, sb + 16 * DLAYERB + (2 * wgi + 1) * 1024, tid, get_partial<2>(PW, 1, pu, pj) + b3r[1], pj < nb, loc);
+        if (kq < 2) store16(u32x4{SENT, SENT, SENT, SENT}, 16 * DLAYERB + (2 * wgi + kq) * 1024 + w * 256 + fi * 16, cbase + ((t + DAHEAD_IH) & (DRING - 1)) * XTB);
+        pp ^= 1;
+        SPX(12);
+    };
+    // RAW, sampling workgroup sidx: the logits of the group's 16 segments gathered into LDS (wave w: rows 128 w .. 128 w + 127), then wave w samples segment
+    // 4 sidx + w (wrnn_raw.h) and publishes x_t as a tagged word; noise row t - noise_t0 of the call's [T][segment][512] noise
+    auto sample_raw = [&]() {
+        const int sb = cbase + 16 * DLAYERB + (t & (DRING - 1)) * XTB;
+        const int sj = 4 * sidx + w, sjc = sj < nb ? sj : nb - 1;
+        float qn[8];
+        const float *qrow = noise_raw + ((size_t)(t - noise_t0) * Nall + b0g + sjc) * C;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qn[e] = qrow[lane + 64 * e];
+        u32x4 x[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, sb, 16 /* sc1 */);
+        if (__builtin_expect(!frag_there(x, live), 0))
+            wait_for([&] { return frag_there(x, live); },
+                     [&] {
+#pragma unroll
+                         for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, sb, 16 /* sc1 */);
+                     },
+                     status, dead, 0x752u, t);
+        SPX(13);
+        {
+            float *lp = LGT + fi * LDC + kbase_lane;
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                *reinterpret_cast<float4 *>(lp + 16 * r) = make_float4(__uint_as_float(x[r].x), __uint_as_float(x[r].y), __uint_as_float(x[r].z), __uint_as_float(x[r].w));
+        }
+        lds_barrier();
+        float lg[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) lg[e] = LGT[sjc * LDC + lane + 64 * e];
+        if (dbgl && sj < nb) {                          // test hook: the 512 logits of every segment
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dbgl[((size_t)t * Nall + b0g + sj) * C + lane + 64 * e] = lg[e];
+        }
+        const int idx = raw_sample512(lg, qn, lane);
+        if (lane == 0 && sj < nb) {
+            float xv = 2.f * (float)idx / ((float)C - 1.f) - 1.f;
+            outp[(size_t)(b0g + sj) * Tall + t] = xv;
+            if (forcex) xv = forcex[(size_t)(b0g + sj) * Tall + t];
+            const u32x2 q = {__float_as_uint(xv), (unsigned)t + 1u};          // one 8-byte word {x_t, tag}: its own flag, two entries, no re-arm
+            __builtin_amdgcn_raw_buffer_store_b64(q, xrs, sj * 8, cbase + 7 * DLAYERB + (t & 1) * XTB, 16 /* sc1 */);
+        }
+        // (LGT is rewritten a step later, behind at least one more workgroup barrier: fc3_raw's)
+        SPX(14);
+    };
 
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
@@ -697,6 +796,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             gh_stage();                                 // (needs h1(t) of every rnn1 workgroup: one hop behind the publication above)
             fc(I1{});
             fc(I2{});
+            if constexpr (!MOL) fc3_raw();
             if (t + 1 < T1) { front_issue(t + 1); front_finish(t + 1); }
         } else {
             // gh(t + 1) is needed at the cell of step t + 1: behind fc2 (and, in the sampling workgroup, behind the sampling) it sits in the
@@ -707,7 +807,12 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             gates_b();
             fc(I1{});
             fc(I2{});
-            if (sampler) sample();
+            if constexpr (MOL) {
+                if (sampler) sample();
+            } else {
+                fc3_raw();
+                if (sampler) sample_raw();
+            }
             gh_stage();
             if (cond_wg && t + CLEAD < T1) cond_step(t + CLEAD);
         }
@@ -742,7 +847,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
 // b is observed to run on XCD b % 8 and the blocks of an XCD to be dealt round-robin over its 32 CUs.  XCD x hosts clusters x (its CUs
 // 0-15) and 8 + x (CUs 16-31); CU c of a cluster: c / 8 = rnn1 | rnn2, unit block c % 8.  Group g of a round runs on cluster g: the first
 // eight groups take one cluster on every XCD.
-template <int NBP, bool FCS, bool PROF>
+template <int NBP, bool FCS, int MODE, bool PROF>
 __global__ __launch_bounds__(NT, 1) void wrnn_sparse_kernel(const LoopArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -782,26 +887,34 @@ __global__ __launch_bounds__(NT, 1) void wrnn_sparse_kernel(const LoopArgs a)
         if (a.tuning & 256) loc = false;                // A/B: everything written through
         __syncthreads();
     }
-    if (cu < 8) sp_role<NBP, FCS, true, PROF>(a, smem, cl, cl, cu, cu, loc);
-    else sp_role<NBP, FCS, false, PROF>(a, smem, cl, cl, cu - 8, cu, loc);
+    if (cu < 8) sp_role<NBP, FCS, MODE, true, PROF>(a, smem, cl, cl, cu, cu, loc);
+    else sp_role<NBP, FCS, MODE, false, PROF>(a, smem, cl, cl, cu - 8, cu, loc);
 }
 
 // clusters of 16 CUs: the kernel's block -> role map is written for the whole 256-CU chip
 int sparse_clusters(int n_cus) { return n_cus >= SPCLUSTERS * SPWG ? SPCLUSTERS : 0; }
 size_t sparse_state_floats() { return (size_t)SPCLUSTERS * SPSTATE_CL; }
 size_t sparse_xbuf_bytes() { return (size_t)SPCLUSTERS * DSLOTB; }      // the regions a launch touches: a prefix of the duo kernel's buffer
-size_t sparse_lds_bytes() { return (size_t)sp_lds().total * sizeof(float); }
+size_t sparse_lds_bytes(int mode) { return (size_t)sp_lds(mode == 0).total * sizeof(float); }
 
-hipError_t launch_sparse(const LoopArgs &args, int nbp, hipStream_t stream)
+template <int MODE>
+const void *sparse_fn(int nbp, bool fcs, bool prof)
 {
-    if ((nbp != 48 && nbp != 64) || !args.fc3f || !args.u1 || !args.xcc_tab || !args.sp_vals || args.NG < 1 || args.NG > SPCLUSTERS) return hipErrorInvalidValue;
-    const size_t lds = sparse_lds_bytes();
+    return fcs ? (nbp == 48 ? (prof ? (const void *)wrnn_sparse_kernel<48, true, MODE, true> : (const void *)wrnn_sparse_kernel<48, true, MODE, false>)
+                            : (prof ? (const void *)wrnn_sparse_kernel<64, true, MODE, true> : (const void *)wrnn_sparse_kernel<64, true, MODE, false>))
+               : (nbp == 48 ? (prof ? (const void *)wrnn_sparse_kernel<48, false, MODE, true> : (const void *)wrnn_sparse_kernel<48, false, MODE, false>)
+                            : (prof ? (const void *)wrnn_sparse_kernel<64, false, MODE, true> : (const void *)wrnn_sparse_kernel<64, false, MODE, false>));
+}
+
+// mode: 1 = MOL, 0 = 9-bit RAW (512 classes: fc3 from fc3_w, the noise of the call in `noise`)
+hipError_t launch_sparse(const LoopArgs &args, int nbp, int mode, hipStream_t stream)
+{
+    if ((nbp != 48 && nbp != 64) || !args.u1 || !args.xcc_tab || !args.sp_vals || args.NG < 1 || args.NG > SPCLUSTERS) return hipErrorInvalidValue;
+    if (mode == 1 ? !args.fc3f : (mode != 0 || args.C != H || !args.noise)) return hipErrorInvalidValue;
+    const size_t lds = sparse_lds_bytes(mode);
     const bool prof = args.prof && !(args.tuning & 64);              // phase clocks (wrnn_options.phase_clocks)
     const bool fcs = args.sp_fc_vals != nullptr;                     // the pack's Linear layers are block-sparse too: gathered fc stages
-    const void *fn = fcs ? (nbp == 48 ? (prof ? (const void *)wrnn_sparse_kernel<48, true, true> : (const void *)wrnn_sparse_kernel<48, true, false>)
-                                      : (prof ? (const void *)wrnn_sparse_kernel<64, true, true> : (const void *)wrnn_sparse_kernel<64, true, false>))
-                         : (nbp == 48 ? (prof ? (const void *)wrnn_sparse_kernel<48, false, true> : (const void *)wrnn_sparse_kernel<48, false, false>)
-                                      : (prof ? (const void *)wrnn_sparse_kernel<64, false, true> : (const void *)wrnn_sparse_kernel<64, false, false>));
+    const void *fn = mode == 1 ? sparse_fn<1>(nbp, fcs, prof) : sparse_fn<0>(nbp, fcs, prof);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     LoopArgs a = args;

@@ -7,8 +7,10 @@ k = int(rows*cols*z).  The WaveRNN paper prunes in BLOCKS (16x1) so the survivin
 16 rows x 1 column, the lowest-scoring fraction z of the blocks of each gate is zeroed.  Applied to `weight_ih_l0` and
 `weight_hh_l0` of rnn1 and rnn2 (the notebook's `prune_rnn_input=True`); biases and the dense layers are untouched.
 
-The loop kernels run the pruned model as masked dense weights (parity: tests/test_gpu_parity.py); a packed block-sparse
-kernel is the follow-up that turns the 95 % zeros into speed (the pruned GRU weights are 0.64 MB and fit a few CUs).
+The dense loop kernels run the pruned model as masked dense weights (parity: tests/test_gpu_parity.py); the block-sparse
+loop kernel (wrnn_sparse_kernel) packs the surviving 16x1 blocks and turns the 95 % zeros into speed: `auto` runs it for a
+MoL model, and for a 9-bit RAW model on request (`model.loop_algo = 'sparse'`; `auto` keeps the dense kernels for RAW,
+whose class indices are compared bit for bit: tests/test_gpu_sparse_raw.py).  8-bit RAW runs on the dense kernels only.
 """
 import numpy as np
 
