@@ -19,8 +19,15 @@ MT19937 stream of the parity tests instead (adds ~25 M host RNG draws per pass).
         bench.py --gpus N --steps K --warmup W             # ... or is launched as one rank of N (RANK / WORLD_SIZE in the env)
     python bench.py --gpus N --corpus config4              # BASELINE config 4: the fixed 64-utterance corpus (942 segments), STRONG scaling
     python bench.py --gpus 1 --steps K --dump-outputs DIR  # ... and write the audio of the last timed step to DIR/*.npy
+    python bench.py --gpus 1 --steps K --warmup W --full   # ... and every leg beyond the headline figure (below)
 
 value = useful audio samples per second over all ranks = N * K * sum(wave_len) / max-over-ranks(time).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: `value`, `ms_per_step` and the
+roofline of the loop kernel in the timed steps.  `--full` adds what takes runs of its own, after the timed steps: config 4's fixed
+corpus over the ranks of the launch (`config.config4`, with the planner's step table), the single-utterance generate() calls, config 3,
+the 8-utterance batch, config 4's per-GPU share at N = 8, the RAW and config-5 legs, the CPU baselines, and `roofline.traffic` from
+the rocprofv3 record of these kernel sources.
 """
 import argparse
 import json
@@ -188,19 +195,22 @@ def main():
     ap.add_argument('--algo', default='auto', choices=['auto', 'loop', 'duo', 'sparse', 'stream'])
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'], help="RAW = 9-bit mu-law ('bits') softmax sampling")
     ap.add_argument('--force-dist', action='store_true', help='initialise a torch.distributed nccl (= RCCL) group even at --gpus 1')
-    ap.add_argument('--no-single', action='store_true', help="skip the single-utterance generate() entries (BASELINE config 2's N=481 / N=1001)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, also run every other leg: config 4 over the ranks, single-utterance calls, config 3, '
+                         'the RAW / config-5 legs, the CPU baselines, the profiled traffic (off: only what the headline figure needs)')
+    ap.add_argument('--no-single', action='store_true', help="--full without the single-utterance generate() entries (BASELINE config 2's N=481 / N=1001) and the legs after them")
     ap.add_argument('--prune', type=float, default=0.0,
                     help='BASELINE config 5: block-prune the GRU matrices (16x1 blocks) to this sparsity, e.g. 0.95')
     ap.add_argument('--prune-linear', action='store_true', help='... and fc1 / fc2 with them, as the reference\'s pruning notebook prunes its Linear layer (the gathered fc stages of wrnn_sparse_kernel)')
     ap.add_argument('--parity-noise', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--corpus', default='batch', choices=['batch', 'config4'],
                     help="batch: --utterances x --frames per GPU (weak scaling).  config4: BASELINE config 4's fixed corpus -- 64 "
                          "utterances of RandomState(2024).randint(300, 901) frames = 942 folded segments, sharded over the ranks "
                          "(strong scaling)")
     ap.add_argument('--corpus-limit', type=int, default=64, help=argparse.SUPPRESS)     # tests: only the first K utterances of config 4
-    ap.add_argument('--no-config4-leg', action='store_true', help="skip the `config.config4` leg (BASELINE config 4's fixed corpus shared by the N ranks)")
+    ap.add_argument('--no-config4-leg', action='store_true', help="--full without the `config.config4` leg (BASELINE config 4's fixed corpus shared by the N ranks)")
     ap.add_argument('--target', type=int, default=11000, help=argparse.SUPPRESS)
     ap.add_argument('--overlap', type=int, default=550, help=argparse.SUPPRESS)
     ap.add_argument('--dry-host', default=None, metavar='MODULE:FACTORY',
@@ -397,7 +407,7 @@ def main():
                        split_rank0=eng.last_run_info(), loop_kernel_ms_rank0=round(eng.last_loop_ms(), 3))
         return out
     c4leg = None
-    if args.corpus == 'batch' and not args.no_config4_leg:
+    if args.full and args.corpus == 'batch' and not args.no_config4_leg:
         try:
             c4leg = config4_leg()
         except Exception as e:
@@ -512,10 +522,11 @@ def main():
         tf = flops_per_launch / (kms * 1e-3) / 1e12
         u_per_wg, ncl, depth = info['units_per_wg'], info['clusters'], info['depth']
         # HBM-side traffic of the loop kernel per pass, from the rocprofv3 PMC passes of THIS command line on THIS source tree
-        # (scripts/summarize_profile.py writes the file; it is ignored unless kernel, geometry and source hash all match)
+        # (scripts/summarize_profile.py writes the file; it is ignored unless kernel, geometry and source hash all match).  --full only
+        # (a plain run reports nothing it did not measure itself)
         traffic = None
         tpath = os.path.join(ROOT, 'profiles', 'traffic_latest.json')
-        if os.path.exists(tpath):
+        if args.full and os.path.exists(tpath):
             tj = json.load(open(tpath))
             if (tj.get('kernel') == info['kernel'] and tj.get('segments') == n_local and tj.get('T') == T and tj.get('mode') == mode
                     and tj.get('source_sha16') == source_sha16()):
@@ -566,7 +577,7 @@ def main():
             res['roofline'], res['roofline_hbm_equivalent'] = mfma, hbm
         else:
             res['roofline'], res['roofline_mfma'] = hbm, mfma
-        if not args.no_single and world == 1 and args.prune == 0 and args.corpus == 'batch':
+        if args.full and not args.no_single and world == 1 and args.prune == 0 and args.corpus == 'batch':
             try:
                 res['config']['single_utterance'] = [single_utterance(481), single_utterance(1001)]
             except Exception as e:
@@ -599,7 +610,7 @@ def main():
                         'mfma_frac': round(2.0 * nnz * 8 * (plan.n_segments // n_utt) * T / (k8 * 1e-3) / 1e12 / MFMA_F32_PEAK_TF, 5)}
                 except Exception as e:
                     res['config']['batch_of_8_utterances'] = {'error': repr(e)}
-        if not args.no_single and world == 1 and args.prune == 0 and args.corpus == 'batch' and mode == 'MOL':
+        if args.full and not args.no_single and world == 1 and args.prune == 0 and args.corpus == 'batch' and mode == 'MOL':
             try:    # BASELINE config 4 is strong scaling: at N = 8 a GPU owns 117-118 of the corpus' 942 segments.  What that share runs at,
                     # on this one GPU (rank 0's block of the fixed 64-utterance corpus, no collective): the rate the 8-GPU number is made of
                 from wavernn_amd.batch import shard_bounds as _sb
@@ -685,7 +696,7 @@ def main():
                 res['config']['config5_gru_only']['vs_dense_value'] = round(res['config']['config5_gru_only']['samples_per_s'] / value, 3)
             res['config']['config5_dense_kernel'] = side_config(block_prune_state_dict(random_state_dict(0, mode='MOL'), 0.95, (16, 1))[0], 'MOL',
                                                                 'BASELINE config 5 on the DENSE wrnn_duo_kernel (algo = duo: the pruned weights as masked dense matrices)', algo2='duo')
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 res['cpu_baseline'] = cpu_baseline(sd, mode, args.frames, target, overlap, args.cpu_seconds)
             except Exception as e:   # the baseline is a report, never a reason to lose the GPU number

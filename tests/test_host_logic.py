@@ -365,18 +365,18 @@ def test_bench_dump_outputs_stays_under_its_budget(tmp_path, monkeypatch):
 
 
 @pytest.mark.parametrize('n', [2, 4, 8])
-def test_bench_default_command_carries_the_config4_leg_dry_host(n):
-    """What the driver's SCALE run issues -- `bench.py --gpus N` and nothing else about the corpus -- measures weak scaling of a batch per
-    GPU AND (round-4 verdict, item 6) a `config.config4` leg: BASELINE config 4's FIXED corpus sharded over the N ranks of the same launch
-    (strong scaling), with the world size the group really had, the ranks the planner used, the block sizes, the time blocked on the
-    all-gather and the post-loop work done under it.  Dry run on the host (gloo, a loop stand-in, the first 5 utterances of the corpus)."""
+def test_bench_full_carries_the_config4_leg_dry_host(n):
+    """`bench.py --gpus N --full` (nothing else about the corpus) measures weak scaling of a batch per GPU AND (round-4 verdict, item 6)
+    a `config.config4` leg: BASELINE config 4's FIXED corpus sharded over the N ranks of the same launch (strong scaling), with the world
+    size the group really had, the ranks the planner used, the block sizes, the time blocked on the all-gather and the post-loop work done
+    under it.  Dry run on the host (gloo, a loop stand-in, the first 5 utterances of the corpus)."""
     import json, subprocess, sys
     from helpers import ROOT
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'tests'), ROOT, os.environ.get('PYTHONPATH', '')]), OMP_NUM_THREADS='1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '1', '--warmup', '0', '--utterances', '1', '--frames', '30',
-           '--target', '550', '--overlap', '55', '--corpus-limit', '5', '--dry-host', 'helpers:probe_loop_fn']
+           '--target', '550', '--overlap', '55', '--corpus-limit', '5', '--full', '--dry-host', 'helpers:probe_loop_fn']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -387,6 +387,23 @@ def test_bench_default_command_carries_the_config4_leg_dry_host(n):
     assert len(per) == n and sum(per) == leg['segments'] and all(x == 0 for x in per[leg['ranks_used']:])
     assert max(per[:leg['ranks_used']]) - min(per[:leg['ranks_used']]) <= 1
     assert leg['ms_per_pass'] > 0 and leg['gather_wait_ms'] >= 0 and leg['unfold_under_gather_ms'] >= 0
+
+
+def test_bench_plain_run_is_only_the_headline_dry_host():
+    """A plain `bench.py --gpus N --steps K --warmup W` runs no leg beyond the headline figure: no `config.config4` leg (that is `--full`),
+    while the headline fields are all there.  Dry run on the host."""
+    import json, subprocess, sys
+    from helpers import ROOT
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'tests'), ROOT, os.environ.get('PYTHONPATH', '')]), OMP_NUM_THREADS='1')
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--utterances', '1', '--frames', '30',
+           '--target', '550', '--overlap', '55', '--corpus-limit', '5', '--dry-host', 'helpers:probe_loop_fn']
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line) and line['ms_per_step'] > 0
+    assert line['n_gpus'] == 2 and 'config4' not in line['config']
 
 
 def test_choose_ranks_fills_the_pipeline_not_the_node():
