@@ -44,11 +44,12 @@ enum { WRNN_MODE_RAW = 0, WRNN_MODE_MOL = 1 };  /* reference: WaveRNN(mode='RAW'
 
 /* Loop kernel selection. */
 enum {
-    WRNN_ALGO_AUTO = 0,     /* shipped dims: WRNN_ALGO_SPARSE when a MOL pack qualifies (wrnn_pack_sparse_blocks() > 0) on a 256-CU device (a qualifying
-                               9-bit RAW pack keeps the dense kernels: WRNN_ALGO_SPARSE runs it on request), else
-                               WRNN_ALGO_CHAIN (MOL or RAW with 512 classes, <= 128 segments, 256 CUs, dense pack), else WRNN_ALGO_DUO (MOL, or RAW
-                               with 512 classes; >= 128 CUs),
-                               else WRNN_ALGO_STREAM; other dims: wrnn_generic_kernel */
+    WRNN_ALGO_AUTO = 0,     /* shipped dims, MOL or RAW with 512 classes: WRNN_ALGO_SPARSE when a MOL pack qualifies (wrnn_pack_sparse_blocks() > 0) on a
+                               device of >= 256 CUs (a qualifying 9-bit RAW pack keeps the dense kernels: WRNN_ALGO_SPARSE runs it on request), else
+                               WRNN_ALGO_CHAIN (<= 128 segments, >= 256 CUs), else WRNN_ALGO_DUO (>= 256 CUs: always its 4 clusters), else
+                               WRNN_ALGO_LOOP (>= 64 CUs: 1 or 2 clusters; also when wrnn_options.clusters asks `auto` for fewer than 4), else -- and for
+                               RAW with another class count -- WRNN_ALGO_STREAM; other dims: wrnn_generic_kernel.  The planner's one table of the
+                               kernels: KINDS in csrc/wrnn_abi.hip */
     WRNN_ALGO_STREAM = 1,   /* one workgroup per folded segment, weights streamed from L2/MALL each step: the generic fallback
                                (any class count, any device size) and the on-GPU cross-check */
     WRNN_ALGO_LOOP = 2,     /* role-split pipelined persistent kernel (RAW and MOL): up to 4 clusters of 64 CUs, each with a full
@@ -56,18 +57,18 @@ enum {
                                tag-free activation exchange in MFMA-fragment order (csrc/wrnn_loop.hip) */
     WRNN_ALGO_DUO = 6,      /* the loop kernel cut for TWO workgroups per CU (MOL and RAW): four roles -- rnn1 / rnn2 x {W_ih + fc, W_hh [+ fc3 and
                                sampling]} -- of <= 128 weight registers, 128 workgroups per 64-CU cluster, so that one wave's MFMAs overlap
-                               the other's loads, pointwise math and barrier waits (csrc/wrnn_duo.hip).  What `auto` runs for a dense pack
-                               beyond 128 segments */
-    WRNN_ALGO_CHAIN = 7,    /* the single-stream latency kernel (MOL and 9-bit RAW, <= 256 segments, 256 CUs): one workgroup per CU, <= 4 groups of <= 16 segments per
-                               64-CU cluster, both halves of a GRU cell's rows in one workgroup (gh never leaves the registers), rnn2 + fc1 + fc2
+                               the other's loads, pointwise math and barrier waits (csrc/wrnn_duo.hip); >= 64 CUs.  What `auto` runs for a dense pack
+                               beyond 128 segments on >= 256 CUs */
+    WRNN_ALGO_CHAIN = 7,    /* the single-stream latency kernel (MOL and 9-bit RAW, >= 256 CUs): one workgroup per CU, <= 4 groups of <= 16 segments in flight per
+                               64-CU cluster (256 segments a round; more: further rounds), both halves of a GRU cell's rows in one workgroup (gh never leaves the registers), rnn2 + fc1 + fc2
                                on one XCD (csrc/wrnn_chain.hip).  What `auto` runs for one utterance (<= 128 segments) of a dense model */
-    WRNN_ALGO_OCTO = 8,     /* the WAVE-SPECIALISED form of the dense loop kernel (MOL, 256 CUs; round 6): ONE 512-thread workgroup per CU -- four matrix
+    WRNN_ALGO_OCTO = 8,     /* the WAVE-SPECIALISED form of the dense loop kernel (MOL, >= 256 CUs, on request only; round 6): ONE 512-thread workgroup per CU -- four matrix
                                waves (W_ih and W_hh of the CU's 16 units in registers, the fc tile in LDS: operand by LDS-DMA, MFMA block, partial tiles)
                                and four service waves (partial sums, GRU cell, publishes, conditioning, fc3 + sampling) that meet through LDS counters;
                                gh never leaves the CU.  Same split, workspace, exchange buffer and state layout as WRNN_ALGO_DUO (csrc/wrnn_octo.hip) */
     WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
                                four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
-                               (wrnn_pack_sparse_blocks) and a 256-CU device; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
+                               (wrnn_pack_sparse_blocks) and >= 256 CUs; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
                                step is the latency of one chain, sixteen chains run side by side (csrc/wrnn_sparse.hip) */
 };
 
@@ -116,7 +117,7 @@ typedef struct wrnn_timer wrnn_timer;
 
 /* What a wrnn_generate* call decided (filled synchronously, before the call returns). */
 typedef struct wrnn_run_info {
-    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" */
+    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_octo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" */
     int32_t units_per_wg;    /* hidden units per workgroup (16; sparse: 64; stream: 0) */
     int32_t clusters;        /* independent CU clusters, each holding one copy of the weights */
     int32_t depth;           /* groups of <= 16 segments in flight per cluster */
@@ -261,6 +262,24 @@ int wrnn_status(void *workspace, void *stream);
  * Call after a run with the same (n_segments, T, n_frames, opt).  Synchronises the device. */
 int wrnn_debug_read_exchange(const wrnn_pack *p, void *workspace, int32_t n_segments, int32_t T, int32_t n_frames,
                              const wrnn_options *opt, int cluster, int slot, int layer, int ring, float *host_out);
+
+/* Test hook: everything the launch planner reads of a pack and its device.  wrnn_pack_create fills one per pack; a test may write one by
+ * hand to plan for a device it does not have. */
+typedef struct wrnn_plan_traits {
+    int32_t struct_bytes;
+    int32_t n_cus;             /* wrnn_device_cus() */
+    int32_t mode, C;           /* WRNN_MODE_*, n_classes */
+    int32_t generic;           /* non-shipped dims (wrnn_generic_kernel only) ... */
+    int32_t gH, gF, gM, gA;    /* ... rnn, fc, feat, aux dims of such a pack (they appear in a message only) */
+    int32_t sp_nbp;            /* 0: the GRU matrices are not block-sparse enough for wrnn_sparse_kernel; else the padded blocks per block row, 48 / 64 */
+    int32_t sp_max_blocks;     /* |wrnn_pack_sparse_blocks()| (a message only) */
+    int32_t sp_fc;             /* 1: fc1 / fc2 are block-sparse too (wrnn_pack_sparse_fc_blocks() > 0).  Recorded; no planning decision reads it */
+} wrnn_plan_traits;
+/* What wrnn_plan_segments (`out`) and wrnn_workspace_bytes_segments (`workspace_bytes`) answer for a pack with these traits: the same
+ * code, return codes and wrnn_last_error() texts, with neither a pack nor a device -- the HIP runtime is not touched.  A step range in
+ * `opt` is validated as wrnn_generate_segments validates it (the other two ignore it). */
+int wrnn_debug_plan(const wrnn_plan_traits *traits, int32_t n_segments, int32_t T, int32_t n_frames,
+                    const wrnn_options *opt, wrnn_run_info *out, size_t *workspace_bytes);
 
 /* Timer objects (see wrnn_options.timer).  wrnn_timer_ms synchronises on the recorded events and returns the SUM of the
  * loop-kernel launch durations of the last call that used the timer, including the calls that continued it with

@@ -7,6 +7,7 @@ fixtures are committed.  Shims: stub `librosa`, alias `np
 configure `hparams`.  Nothing is written into the reference tree.
 
     python scripts/make_golden.py
+    python scripts/make_golden.py planner_table     # tests/golden/planner_table.npz only: the built library's launch planner, no reference needed
 """
 import os, sys, types
 import numpy as np
@@ -15,6 +16,99 @@ sys.dont_write_bytecode = True
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 REF = os.environ.get('WRNN_REFERENCE', '/root/reference')
+
+
+# ---- tests/golden/planner_table.npz: the launch planner, recorded through wrnn_debug_plan.  Needs the built library only (neither a GPU
+# nor the reference): `python scripts/make_golden.py planner_table` leaves before the reference is imported. ------------------------------
+PLAN_TRAITS = ('n_cus', 'mode', 'C', 'generic', 'gH', 'gF', 'gM', 'gA', 'sp_nbp', 'sp_max_blocks', 'sp_fc')
+PLAN_CALL = ('algo', 'n_segments', 'T', 'n_frames', 'depth', 'clusters', 'slab_steps', 't_begin', 't_end')
+PLAN_OUT = ('rc', 'kernel', 'units_per_wg', 'clusters', 'depth', 'rounds', 'slab_steps', 'workspace_bytes', 'error')
+PLAN_CUS = (32, 64, 128, 192, 255, 256, 304)
+PLAN_PACKS = dict(                    # mode: 0 RAW, 1 MOL
+    dense_mol=dict(mode=1, C=30, sp_max_blocks=512),
+    dense_raw512=dict(mode=0, C=512, sp_max_blocks=512),
+    raw256=dict(mode=0, C=256, sp_max_blocks=512),
+    sparse_mol_48=dict(mode=1, C=30, sp_nbp=48, sp_max_blocks=40),
+    sparse_mol_64=dict(mode=1, C=30, sp_nbp=64, sp_max_blocks=60),
+    sparse_mol_64_fc=dict(mode=1, C=30, sp_nbp=64, sp_max_blocks=60, sp_fc=1),
+    sparse_raw512=dict(mode=0, C=512, sp_nbp=64, sp_max_blocks=60, sp_fc=1),
+    generic=dict(mode=1, C=30, generic=1, gH=256, gF=256, gM=80, gA=32, sp_max_blocks=256))
+PLAN_ALGOS = (0, 1, 2, 5, 6, 7, 8, 3, 4, 9)         # auto, stream, loop, sparse, duo, chain, octo; 3, 4, 9: unknown
+PLAN_SEGMENTS = (1, 16, 17, 64, 65, 128, 129, 256, 257, 300, 512, 513, 942, 4096, 43690, 43691)     # the last two: either side of the 2 GB aux-table refusal
+
+
+def planner_cases():
+    """The rows of the table, as dicts of PLAN_TRAITS + PLAN_CALL: the full cross of device size x pack x algo x segment count at default
+    options, and the option axes (depth x clusters; T x slab_steps x n_frames; step ranges) on fewer devices and packs."""
+    from itertools import product
+    rows = []
+
+    def add(cus, pack, algo, n, T=12100, n_frames=700, depth=0, clusters=0, slab_steps=0, t_range=(0, 0)):
+        rows.append(dict(dict.fromkeys(PLAN_TRAITS, 0), **PLAN_PACKS[pack], n_cus=cus, algo=algo, n_segments=n, T=T, n_frames=n_frames, depth=depth,
+                         clusters=clusters, slab_steps=slab_steps, t_begin=t_range[0], t_end=t_range[1]))
+    for cus, pack, algo, n in product(PLAN_CUS, PLAN_PACKS, PLAN_ALGOS, PLAN_SEGMENTS):
+        add(cus, pack, algo, n)
+    for cus, pack, algo, n, depth, clusters in product((128, 256, 304), ('dense_mol', 'dense_raw512', 'sparse_mol_64_fc'), (0, 2, 5, 6, 7, 8),
+                                                       (1, 65, 300, 942), (0, 1, 2, 3, 4, 8, 9), (0, 1, 2, 3, 4)):
+        add(cus, pack, algo, n, depth=depth, clusters=clusters)
+    for cus, pack, algo, n, T, slab, nf in product((64, 256), ('dense_mol', 'dense_raw512', 'raw256', 'sparse_mol_64', 'generic'), PLAN_ALGOS[:7],
+                                                   (1, 129, 942), (1, 100, 12100), (0, 97, 5000), (1, 700)):
+        add(cus, pack, algo, n, T=T, n_frames=nf, slab_steps=slab)
+    for cus, pack, algo, n, rng in product((32, 256), ('dense_mol', 'raw256', 'sparse_mol_48', 'generic'), (0, 1, 2, 5, 6, 7, 9), (1, 300),
+                                           ((0, 0), (10, 60), (0, 100), (60, 10), (-1, 50), (0, 101), (100, 100))):
+        add(cus, pack, algo, n, T=100, t_range=rng)
+    return rows
+
+
+def plan_one(L, row):
+    """One row through wrnn_debug_plan -> (rc, kernel name, units_per_wg, clusters, depth, rounds, slab_steps, workspace bytes, error text)."""
+    import ctypes
+    from wavernn_amd import _lib
+    t = _lib.PlanTraits(**{k: row[k] for k in PLAN_TRAITS})
+    o = _lib.Options(algo=row['algo'], depth=row['depth'], clusters=row['clusters'], slab_steps=row['slab_steps'], t_begin=row['t_begin'],
+                     t_end=row['t_end'])
+    i, ws = _lib.RunInfo(), ctypes.c_size_t(0)
+    rc = L.wrnn_debug_plan(ctypes.byref(t), row['n_segments'], row['T'], row['n_frames'], ctypes.byref(o), ctypes.byref(i), ctypes.byref(ws))
+    if rc != 0:
+        return (rc, None, 0, 0, 0, 0, 0, 0, L.wrnn_last_error().decode())
+    return (rc, i.kernel.decode(), i.units_per_wg, i.clusters, i.depth, i.rounds, i.slab_steps, ws.value, None)
+
+
+def planner_table():
+    import io, zipfile
+    from wavernn_amd import _lib
+    L = _lib.lib()
+    rows = planner_cases()
+    kernels, errors, outs = [], [], []
+    for r in rows:
+        res = list(plan_one(L, r))
+        for col, names in ((1, kernels), (8, errors)):      # names -> indices into de-duplicated lists (-1: none)
+            if res[col] is None:
+                res[col] = -1
+            else:
+                if res[col] not in names:
+                    names.append(res[col])
+                res[col] = names.index(res[col])
+        outs.append(res)
+    arrays = dict(traits=np.array([[r[k] for k in PLAN_TRAITS] for r in rows], np.int32), trait_names=np.array(PLAN_TRAITS),
+                  call=np.array([[r[k] for k in PLAN_CALL] for r in rows], np.int32), call_names=np.array(PLAN_CALL),
+                  out=np.array(outs, np.int64), out_names=np.array(PLAN_OUT), kernels=np.array(kernels), errors=np.array(errors))
+    # an .npz with fixed member dates: the same table gives the same file, byte for byte
+    path = os.path.join(REPO, 'tests', 'golden', 'planner_table.npz')
+    with zipfile.ZipFile(path, 'w') as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, a, allow_pickle=False)
+            zi = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(zi, buf.getvalue())
+    print('planner table:', len(rows), 'rows,', len(kernels), 'kernels,', len(errors), 'error texts,', os.path.getsize(path), 'bytes')
+
+
+if __name__ == '__main__' and sys.argv[1:] == ['planner_table']:
+    planner_table()
+    sys.exit(0)
+
 sys.path.insert(0, REF)
 lib = types.ModuleType('librosa'); lib.output = types.SimpleNamespace(write_wav=lambda *a, **k: None)
 sys.modules['librosa'] = lib

@@ -761,6 +761,37 @@ def test_planner_picks_the_kernel_by_pack_and_batch(gpu):
         assert eng.workspace_bytes(n, 12100, 700) == eng.workspace_bytes(n, 121000, 70000) < 300e6
 
 
+def test_debug_plan_answers_what_the_pack_entry_points_answer(gpu):
+    """`wrnn_debug_plan` on traits read off a real pack and this device == `wrnn_plan_segments` + `wrnn_workspace_bytes_segments` on the pack,
+    field for field, refusals (code and text) included: what tests/test_planner_table.py pins on the CPU is the path the product runs.
+    Nothing is launched."""
+    import ctypes
+    from wavernn_amd import _lib
+    from wavernn_amd.engine import LoopEngine
+    from wavernn_amd.prune import block_prune_state_dict
+    from wavernn_amd.synthetic import random_state_dict
+    sd = random_state_dict(3, mode='MOL')
+    engines = (LoopEngine(sd, 'MOL', device=gpu), LoopEngine(block_prune_state_dict(sd, 0.95, (16, 1))[0], 'MOL', device=gpu))
+    assert engines[0].sparse_blocks < 0 < engines[1].sparse_blocks
+    fields = ('units_per_wg', 'clusters', 'depth', 'rounds', 'slab_steps', 'launches')
+    for eng in engines:
+        L, blocks, fc = eng.lib, eng.sparse_blocks, eng.sparse_fc_blocks
+        traits = _lib.PlanTraits(n_cus=L.wrnn_device_cus(gpu.index), mode=_lib.MODE_MOL, C=eng.n_classes, sp_max_blocks=abs(blocks), sp_fc=int(fc > 0),
+                                 sp_nbp=0 if blocks <= 0 else (64 if blocks > 48 or fc > 48 else 48))
+        for n in (1, 65, 129, 257):
+            for algo in ('auto', 'duo', 'chain', 'sparse'):
+                o = _lib.Options(algo=_lib.ALGOS[algo])
+                a, b, ws = _lib.RunInfo(), _lib.RunInfo(), ctypes.c_size_t(0)
+                rc_a = L.wrnn_plan_segments(eng._pack, n, 100, ctypes.byref(o), ctypes.byref(a))
+                err_a = L.wrnn_last_error()
+                ws_a = L.wrnn_workspace_bytes_segments(eng._pack, n, 100, 700, ctypes.byref(o))
+                rc_b = L.wrnn_debug_plan(ctypes.byref(traits), n, 100, 700, ctypes.byref(o), ctypes.byref(b), ctypes.byref(ws))
+                assert rc_a == rc_b and ws_a == ws.value and (ws_a > 0) == (rc_a == 0), (n, algo, rc_a, rc_b, ws_a, ws.value)
+                assert a.kernel == b.kernel and [getattr(a, f) for f in fields] == [getattr(b, f) for f in fields], (n, algo)
+                if rc_a != 0:
+                    assert err_a == L.wrnn_last_error() != b'', (n, algo, err_a)
+
+
 def test_config1_raw_unbatched_one_second(gpu, tmp_path):
     """BASELINE config 1 geometry: 9-bit mu-law WaveRNN, unbatched generate on 1 s of random mel (81 frames -> 22,275
     steps, one segment) -- `generate()` end to end against the oracle's end-to-end restatement, bit-exact."""

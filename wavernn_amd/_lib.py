@@ -22,7 +22,7 @@ ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': 
 EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_create', 'wrnn_pack_destroy',
            'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
            'wrnn_generate_segments', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
-           'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
+           'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
            'wrnn_taco_last_error', 'wrnn_bigru']
@@ -74,6 +74,16 @@ class Geometry(ctypes.Structure):
 class RunInfo(ctypes.Structure):
     _fields_ = [('kernel', ctypes.c_char_p)] + \
                [(n, ctypes.c_int32) for n in ('units_per_wg', 'clusters', 'depth', 'rounds', 'slab_steps', 'launches')]
+
+
+class PlanTraits(ctypes.Structure):
+    """wrnn_plan_traits (include/wavernn_amd.h): what the launch planner reads of a pack and its device (wrnn_debug_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_bytes', 'n_cus', 'mode', 'C', 'generic', 'gH', 'gF', 'gM', 'gA', 'sp_nbp', 'sp_max_blocks',
+                                              'sp_fc')]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = ctypes.sizeof(PlanTraits)
 
 
 class Options(ctypes.Structure):
@@ -163,6 +173,8 @@ def lib():
     L.wrnn_debug_read_exchange.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.POINTER(Options), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_void_p]
+    L.wrnn_debug_plan.argtypes = [ctypes.POINTER(PlanTraits), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Options),
+                                  ctypes.POINTER(RunInfo), ctypes.POINTER(ctypes.c_size_t)]
     L.wrnn_pre_create.argtypes = [ctypes.POINTER(PreWeights), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_pre_destroy.argtypes = [ctypes.c_void_p]
     L.wrnn_pre_destroy.restype = None

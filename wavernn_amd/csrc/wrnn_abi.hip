@@ -20,12 +20,10 @@ hipError_t launch_noise_mol(const float *in, float *out, long n, int B, int n_cu
 hipError_t launch_stream(const LoopArgs &args, int mode, hipStream_t stream);
 hipError_t launch_loop(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int loop_max_depth(int mode);
-int loop_clusters(int n_cus);
 size_t loop_state_floats(int G);
 hipError_t launch_generic(const GenArgs &args, int mode, hipStream_t stream);
 bool generic_dims_ok(int H, int F, int M, int A, int C, int mode);
 hipError_t launch_duo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
-int duo_clusters(int n_cus);
 int duo_max_depth();
 size_t duo_xbuf_bytes(int G);
 size_t duo_xbuf_bytes_max();
@@ -36,7 +34,6 @@ size_t sparse_xbuf_bytes();
 hipError_t launch_put_floats(float *dst, const float *src, int n, hipStream_t stream);
 hipError_t launch_chain(const LoopArgs &args, int mode, hipStream_t stream);
 hipError_t launch_octo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
-int octo_clusters(int n_cus);
 int octo_max_depth();
 int chain_clusters(int n_cus);
 int chain_max_depth();
@@ -68,7 +65,8 @@ static void set_err(const char *fmt, ...)
     } while (0)
 
 struct wrnn_pack {
-    int device, n_cus, C, mode;
+    int device;
+    wrnn_plan_traits tr;       // everything the launch planner reads (make_plan, ws_layout): n_cus, mode, C, generic + dims, sp_nbp, sp_max_blocks
     size_t weight_bytes;
     char *dev;          // one allocation
     size_t dev_bytes;
@@ -80,11 +78,7 @@ struct wrnn_pack {
     const float *fc3f;         // MOL: fc3.weight in A-fragment order (wrnn_duo.hip)
     const float *u1;           // MOL: rnn1.weight_ih . I.weight[:,0] [3H] -- the x_{t-1} term of rnn1's gi (wrnn_duo.hip)
     // dimension-generic pack (any hparams but the shipped ones): only the k-major copies + biases, run by wrnn_generic_kernel
-    bool generic;
-    int gH, gF, gM, gA;
     const float *g_I_T, *g_fc1T, *g_fc2T, *g_w_ih2T;      // (the other k-major copies are the fields above)
-    int sp_nbp;                // 0 = the GRU matrices are not block-sparse enough for wrnn_sparse_kernel; else 48 / 64
-    int sp_max_blocks;
     const float *sp_vals;
     const int *sp_cols;
     int sp_fc_max_blocks;      // fc1 / fc2 (columns [0, H): the aux columns live in the per-frame tables): largest block row
@@ -167,8 +161,8 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         b.add(nullptr, 64);
         wrnn_pack *p = new wrnn_pack();
         memset(p, 0, sizeof *p);
-        p->device = device; p->n_cus = cus; p->C = C; p->mode = w->mode; p->generic = true;
-        p->gH = gH; p->gF = gF; p->gM = gM; p->gA = gA;
+        p->device = device; p->tr.n_cus = cus; p->tr.C = C; p->tr.mode = w->mode; p->tr.generic = 1;
+        p->tr.gH = gH; p->tr.gF = gF; p->tr.gM = gM; p->tr.gA = gA;
         p->dev_bytes = b.host.size() * sizeof(float);
         p->weight_bytes = sizeof(float) * ((size_t)gH * (1 + gM + gA) + gH + 2 * ((size_t)3 * gH * gH) + (size_t)3 * gH * (gH + gA) + (size_t)3 * gH * gH +
                                            4 * 3 * gH + (size_t)gF * (gH + gA) + (size_t)gF * (gF + gA) + 2 * gF + (size_t)C * gF + C);
@@ -182,7 +176,8 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         p->g_w_ih2T = base + o2i; p->w_hh2T = base + o2h; p->b_ih2 = base + o2bi; p->b_hh2 = base + o2bh;
         p->g_fc1T = base + of1; p->fc1_b = base + of1b; p->g_fc2T = base + of2; p->fc2_b = base + of2b;
         p->fc3T = base + of3; p->fc3_b = base + of3b;
-        p->sp_max_blocks = gH;
+        p->tr.sp_max_blocks = gH;
+        p->tr.struct_bytes = (int32_t)sizeof p->tr;
         *out = p;
         return WRNN_OK;
     }
@@ -305,7 +300,7 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
     b.add(nullptr, 64);   // tail padding so vector loads past the last array stay inside the allocation
 
     wrnn_pack *p = new wrnn_pack();
-    p->device = device; p->n_cus = cus; p->C = C; p->mode = w->mode;
+    p->device = device; p->tr.n_cus = cus; p->tr.C = C; p->tr.mode = w->mode;
     p->dev_bytes = b.host.size() * sizeof(float);
     // W of SURVEY.md section 8(d): every loop parameter the reference touches per step
     p->weight_bytes = sizeof(float) * ((size_t)H * KI + H + 2 * ((size_t)3 * H * H) + (size_t)3 * H * K2 + (size_t)3 * H * H +
@@ -325,12 +320,13 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
     p->c2_wT = base + o_c2_wT; p->c3_wT = base + o_c3_wT; p->c4_wT = base + o_c4_wT;
     p->fc3f = w->mode == WRNN_MODE_MOL ? base + o_fc3f : nullptr;
     p->u1 = base + o_u1;
-    p->sp_nbp = sp_nbp; p->sp_max_blocks = sp_max;
+    p->tr.sp_nbp = sp_nbp; p->tr.sp_max_blocks = sp_max;
     p->sp_vals = sp_nbp ? base + o_spv : nullptr;
     p->sp_cols = sp_nbp ? reinterpret_cast<const int *>(base + o_spc) : nullptr;
     p->sp_fc_max_blocks = sp_fc_max;
     p->sp_fc_vals = sp_fc_ok ? base + o_sfv : nullptr;
     p->sp_fc_cols = sp_fc_ok ? reinterpret_cast<const int *>(base + o_sfc) : nullptr;
+    p->tr.struct_bytes = (int32_t)sizeof p->tr; p->tr.sp_fc = sp_fc_ok ? 1 : 0;
     *out = p;
     return WRNN_OK;
 }
@@ -344,7 +340,7 @@ extern "C" void wrnn_pack_destroy(wrnn_pack *p)
 
 extern "C" size_t wrnn_pack_weight_bytes(const wrnn_pack *p) { return p ? p->weight_bytes : 0; }
 
-extern "C" int wrnn_pack_sparse_blocks(const wrnn_pack *p) { return p ? (p->sp_nbp ? p->sp_max_blocks : -p->sp_max_blocks) : 0; }
+extern "C" int wrnn_pack_sparse_blocks(const wrnn_pack *p) { return p ? (p->tr.sp_nbp ? p->tr.sp_max_blocks : -p->tr.sp_max_blocks) : 0; }
 extern "C" int wrnn_pack_sparse_fc_blocks(const wrnn_pack *p) { return p ? (p->sp_fc_vals ? p->sp_fc_max_blocks : -p->sp_fc_max_blocks) : 0; }
 
 struct wrnn_timer {
@@ -426,22 +422,59 @@ int enqueue_progress(const wrnn_options *o, int done, int T, int n, hipStream_t 
     return WRNN_OK;
 }
 
-enum Kind { K_STREAM, K_LOOP, K_SPARSE, K_DUO, K_GENERIC, K_CHAIN };
-constexpr int DUO_TAB_FPS = 8;       // wrnn_duo_kernel: rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
+enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, N_KINDS };
+constexpr int DUO_TAB_FPS = 8;       // rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
 constexpr bool DUO_AUTO = true;      // `auto` runs MoL on wrnn_duo_kernel at every depth (round 4, profiles/r04a_probe_new.json: 13.5 vs 16.6 us per step
+                                     // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
 constexpr int CHAIN_AUTO_GROUPS = 8;   // `auto` runs calls of up to this many groups (128 segments) on wrnn_chain_kernel: one / two groups per cluster, 10.4 / 13.8 us (RAW: 12.8 / 16.3)
                                        // per step against wrnn_duo_kernel's 12.2 / 16.9; from three groups on the duo kernel wins (profiles/r05i_probe_chain_depths.json)
 constexpr bool OCTO_AUTO = false;    // `auto` runs dense MoL batches beyond wrnn_chain_kernel's range on wrnn_octo_kernel (round 6)
-constexpr int DUO_MIN_DEPTH = 1;     // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
+
+// Everything the host knows of a kernel, once: what make_plan, ws_layout, wrnn_plan_segments and wrnn_generate_segments look up by Kind.
+struct KindDesc {
+    const char *name;
+    int units_per_wg;                   // as wrnn_run_info reports it
+    int kind_tag;                       // LoopArgs.kind_tag: status word 8, which a continued call must find again
+    bool persistent;                    // state and exchange buffer live in the workspace between launches: split into clusters x depth x rounds, slabs of steps,
+                                        // and the only kernels that accept a partial step range
+    bool slabbed;                       // ... and forms its conditioning in the loop, from per-segment aux tables refilled for every slab
+    bool mel_stage;                     // ... and can form the last up-sampling stage too (wrnn_options.mel_stage)
+    int (*clusters)(int n_cus);         // 0: the device cannot host it
+    int (*max_depth)(int mode);
+    size_t (*state_floats)(int G);      // per round
+    size_t (*xbuf_bytes)(int G);        // exchange buffer: what the workspace holds ...
+    size_t (*xbuf_fill)(int G);         // ... and the prefix a launch at depth G touches (set to the sentinel before it)
+    hipError_t (*launch)(const LoopArgs &a, int ncl, int nbp, int mode, hipStream_t s);
+};
+size_t loop_xbuf_bytes(int) { return XBUF_FLOATS * sizeof(float); }
+const KindDesc KINDS[N_KINDS] = {
+    /* K_STREAM  */ {"wrnn_stream_kernel", 0, 0, false, false, false},
+    /* K_GENERIC */ {"wrnn_generic_kernel", 16, 0, false, false, false},
+    /* K_LOOP    */ {"wrnn_loop_kernel", 16, 1, true, false, false, clusters_of_64, loop_max_depth, loop_state_floats, loop_xbuf_bytes, loop_xbuf_bytes,
+                     [](const LoopArgs &a, int ncl, int, int mode, hipStream_t s) { return launch_loop(a, ncl, mode, s); }},
+    // (wrnn_duo_kernel's launches may differ in depth: the workspace holds all 8 x 4 regions)
+    /* K_DUO     */ {"wrnn_duo_kernel", 16, 2, true, true, true, clusters_of_64, [](int) { return duo_max_depth(); }, loop_state_floats,
+                     [](int) { return duo_xbuf_bytes_max(); }, duo_xbuf_bytes,
+                     [](const LoopArgs &a, int ncl, int, int mode, hipStream_t s) { return launch_duo(a, ncl, mode, s); }},
+    // (one 512-thread workgroup per CU, matrix + service waves; MOL: the duo kernel's split, workspace, exchange buffer and state layout, to the depth its LDS carve holds)
+    /* K_OCTO    */ {"wrnn_octo_kernel", 16, 5, true, true, true, clusters_of_64, [](int) { return octo_max_depth(); }, loop_state_floats,
+                     [](int) { return duo_xbuf_bytes_max(); }, duo_xbuf_bytes,
+                     [](const LoopArgs &a, int ncl, int, int mode, hipStream_t s) { return launch_octo(a, ncl, mode, s); }},
+    /* K_CHAIN   */ {"wrnn_chain_kernel", 16, 4, true, true, true, chain_clusters, [](int) { return chain_max_depth(); }, chain_state_floats,
+                     chain_xbuf_bytes, chain_xbuf_bytes,
+                     [](const LoopArgs &a, int, int, int mode, hipStream_t s) { return launch_chain(a, mode, s); }},
+    // (16 clusters of 16 CUs, one group each)
+    /* K_SPARSE  */ {"wrnn_sparse_kernel", 64, 3, true, true, true, sparse_clusters, [](int) { return 1; }, [](int) { return sparse_state_floats(); },
+                     [](int) { return sparse_xbuf_bytes(); }, [](int) { return sparse_xbuf_bytes(); },
+                     [](const LoopArgs &a, int, int nbp, int mode, hipStream_t s) { return launch_sparse(a, nbp, mode, s); }},
+};
 
 // what a call will run: kernel, split, rounds, slab length
 struct Plan {
     Kind kind;
     int ncl, G, rounds, per_round, slab, ngr_max;
-    int tab_fps;                        // K_DUO: rows per segment of the per-slab aux tables
+    int tab_fps;                        // slabbed kernels: rows per segment of the per-slab aux tables
     int t0, t1;
-    bool octo;                          // K_DUO planned onto wrnn_octo_kernel (one 512-thread workgroup per CU: matrix + service waves; MOL): the same split,
-                                        // workspace, exchange buffer and state layout
 };
 
 struct WsLayout {
@@ -452,29 +485,72 @@ struct WsLayout {
 };
 size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
-const wrnn_options *norm_options(const wrnn_options *opt, wrnn_options *tmp)
+// a caller's struct, of this or another version of the header: its first struct_bytes bytes, the rest zero (NULL: all defaults)
+template <class S> S norm_struct(const S *in)
 {
-    memset(tmp, 0, sizeof *tmp);
-    if (opt) {
-        size_t n = opt->struct_bytes > 0 ? (size_t)opt->struct_bytes : sizeof *tmp;
-        if (n > sizeof *tmp) n = sizeof *tmp;
-        memcpy(tmp, opt, n);
-    }
-    tmp->struct_bytes = (int32_t)sizeof *tmp;
-    return tmp;
+    S s;
+    memset(&s, 0, sizeof s);
+    if (in) memcpy(&s, in, in->struct_bytes > 0 && (size_t)in->struct_bytes < sizeof s ? (size_t)in->struct_bytes : sizeof s);
+    s.struct_bytes = (int32_t)sizeof s;
+    return s;
+}
+// ... and planned as the WHOLE call: the workspace and the split of a partial-range call are the whole call's
+wrnn_options whole_call(const wrnn_options *opt)
+{
+    wrnn_options o = norm_struct(opt);
+    o.t_begin = 0; o.t_end = 0;
+    return o;
 }
 
-// kernel choice: the block-sparse kernel if the pack qualifies (MOL, every 16-row block row of the GRU matrices keeps <= 64 columns) on a
-// 256-CU device (a qualifying 9-bit RAW pack runs on it on request only: algo = sparse), else the two-workgroups-per-CU loop kernel (RAW with 512 classes or MOL, >= 128 CUs), else the one-per-CU loop kernel,
-// else stream
-int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
+// B segments = groups of <= SEG on ncl clusters x G slots: the requested depth, or as deep as the segments fill evenly -- rounds =
+// ceil(groups / (ncl * gmax)), then the shallowest depth that still needs only that many rounds (deeper pipelines hide the exchange
+// latency; empty slots cost nothing) --, then balanced rounds of whole segments, every round cut into <= ncl * G groups
+void plan_split(Plan *pl, int B, int ncl, int gmax, int depth)
+{
+    const int groups = (B + SEG - 1) / SEG;
+    int g = depth;
+    if (g < 1 || g > gmax) {
+        const int rounds = (groups + ncl * gmax - 1) / (ncl * gmax);
+        g = (groups + ncl * rounds - 1) / (ncl * rounds);
+        if (g < 1) g = 1;
+        if (g > gmax) g = gmax;
+    }
+    pl->ncl = ncl; pl->G = g;
+    pl->rounds = (groups + ncl * g - 1) / (ncl * g);
+    pl->per_round = (B + pl->rounds - 1) / pl->rounds;
+    pl->ngr_max = (pl->per_round + SEG - 1) / SEG;
+    if (pl->ngr_max > ncl * g) { pl->rounds += 1; pl->per_round = (B + pl->rounds - 1) / pl->rounds; pl->ngr_max = (pl->per_round + SEG - 1) / SEG; }
+}
+
+// steps per slab when the caller names none = what a slab holds: wrnn_loop_kernel -- the hoisted conditioning cI (2 KB per segment-step) + the
+// derived MoL noise; the slabbed kernels form cI in the loop: only the derived noise (44 B per segment-step)
+int default_slab(const Plan &pl, int mode)
+{
+    const int most = KINDS[pl.kind].slabbed ? 4096 : 1024;
+    int slab = most;
+    if (!KINDS[pl.kind].slabbed) slab = (int)((96u << 20) / ((size_t)pl.ngr_max * SEG * H * sizeof(float)));
+    else if (mode == WRNN_MODE_MOL) slab = (int)((32u << 20) / ((size_t)pl.per_round * 11 * sizeof(float) * pl.rounds));
+    return slab < 16 ? 16 : slab > most ? most : slab;
+}
+
+// Which kernel a call runs on, and how it is cut.  algo = a kernel by name: that kernel, or an error that says what it needs (WRNN_ERR_ARG: this
+// pack never runs on it; WRNN_ERR_RESIDENCY: this device is too small).  `auto`, shipped dims, MOL or RAW with 512 classes:
+//   a MOL pack whose GRU matrices are block-sparse (sp_nbp), >= 256 CUs                      wrnn_sparse_kernel (a sparse RAW pack: on request only)
+//   else up to CHAIN_AUTO_GROUPS groups (128 segments), >= 256 CUs                           wrnn_chain_kernel
+//   else >= 256 CUs                                                                          wrnn_duo_kernel, always on 4 clusters
+//   else >= 64 CUs                                                                           wrnn_loop_kernel on 1 or 2 clusters, no more than there are groups
+//   else, and RAW with another class count                                                   wrnn_stream_kernel
+// non-shipped dims: wrnn_generic_kernel.  wrnn_duo_kernel on 1 or 2 clusters (>= 64 CUs) and wrnn_octo_kernel (MOL, >= 256 CUs) run on request only.
+// wrnn_options.depth is honoured up to the kernel's max_depth; .clusters (1, 2, 4) only where loop / duo / octo is planned (`auto` on fewer than 4
+// clusters: wrnn_loop_kernel).
+int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Plan *pl)
 {
     const bool shape_ok = (p->mode == WRNN_MODE_MOL) || (p->C == H);
     pl->t0 = o->t_begin; pl->t1 = o->t_end;
     if (pl->t0 == 0 && pl->t1 == 0) pl->t1 = T;
     if (pl->t0 < 0 || pl->t1 > T || pl->t0 >= pl->t1) { set_err("bad step range [%d, %d) of T=%d", pl->t0, pl->t1, T); return WRNN_ERR_ARG; }
+    const bool partial = pl->t0 != 0 || pl->t1 != T;
     const int algo = o->algo;
-    pl->octo = false;
     if (algo != WRNN_ALGO_AUTO && algo != WRNN_ALGO_STREAM && algo != WRNN_ALGO_LOOP && algo != WRNN_ALGO_SPARSE && algo != WRNN_ALGO_DUO && algo != WRNN_ALGO_CHAIN &&
         algo != WRNN_ALGO_OCTO) {
         set_err("unknown algo %d", algo);
@@ -487,139 +563,81 @@ int make_plan(const wrnn_pack *p, int B, int T, const wrnn_options *o, Plan *pl)
             set_err("this pack has non-shipped dims (rnn %d, fc %d, feat %d, aux %d): only the generic kernel (algo auto / stream) runs it", p->gH, p->gF, p->gM, p->gA);
             return WRNN_ERR_ARG;
         }
-        if (pl->t0 != 0 || pl->t1 != T) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
+        if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
         pl->kind = K_GENERIC;
         return WRNN_OK;
     }
-    // wrnn_chain_kernel (MOL and 9-bit RAW, 256 CUs): one workgroup per CU, one instruction stream per wave.  `auto`: <= 128 segments -- <= 64 (one utterance
-    // of BASELINE config 2 / 3): one group per 64-CU cluster, a step is the latency of one chain; <= 128: two groups per cluster --; on
-    // request (algo = chain) also with up to 4 groups in flight per cluster (wrnn_options.depth) and rounds beyond that
-    const int ccl = chain_clusters(p->n_cus);
+    // ---- what was asked for by name must be possible
+    const int ccl = KINDS[K_CHAIN].clusters(p->n_cus), scl = KINDS[K_SPARSE].clusters(p->n_cus), lcl = KINDS[K_LOOP].clusters(p->n_cus);
     const bool chain_hw = shape_ok && ccl >= 1;
     if (algo == WRNN_ALGO_CHAIN && !chain_hw) {
         set_err("wrnn_chain_kernel needs MOL or RAW with 512 classes, and >= 256 CUs (C = %d, device: %d CUs)", p->C, p->n_cus);
         return !shape_ok ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
     }
-    const bool sparse_auto = p->sp_nbp && p->mode == WRNN_MODE_MOL;      // (RAW: the sparse kernel's summation order is not the oracle's -- `auto` keeps the dense kernels)
-    if (algo == WRNN_ALGO_CHAIN || (algo == WRNN_ALGO_AUTO && chain_hw && groups <= CHAIN_AUTO_GROUPS && !sparse_auto)) {
-        const int gmax = chain_max_depth();
-        int g = o->depth;
-        if (g < 1 || g > gmax) {
-            const int rounds = (groups + ccl * gmax - 1) / (ccl * gmax);
-            g = (groups + ccl * rounds - 1) / (ccl * rounds);
-            if (g < 1) g = 1;
-            if (g > gmax) g = gmax;
-        }
-        pl->kind = K_CHAIN; pl->ncl = ccl; pl->G = g;
-        pl->rounds = (groups + ccl * g - 1) / (ccl * g);
-        pl->per_round = (B + pl->rounds - 1) / pl->rounds;
-        pl->ngr_max = (pl->per_round + SEG - 1) / SEG;
-        if (pl->ngr_max > ccl * g) { pl->rounds += 1; pl->per_round = (B + pl->rounds - 1) / pl->rounds; pl->ngr_max = (pl->per_round + SEG - 1) / SEG; }
-        int slab = o->slab_steps;
-        if (slab < 1) {                      // (an explicit slab length is taken as given -- short slabs included: tests -- as the duo branch does)
-            slab = p->mode == WRNN_MODE_MOL ? (int)((32u << 20) / ((size_t)pl->per_round * 11 * sizeof(float) * pl->rounds)) : 4096;
-            if (slab < 16) slab = 16;
-            if (slab > 4096) slab = 4096;
-        }
-        if (slab > T) slab = T;
-        pl->slab = slab;
-        pl->tab_fps = DUO_TAB_FPS;
-    }
-    // a block-sparse pack runs on wrnn_sparse_kernel (round 5: 16 clusters of 16 CUs, one group of 16 segments each -- the step is the
-    // latency of one chain, and sixteen chains run side by side): `auto` picks it whenever a MOL pack and the device qualify
-    const int scl = sparse_clusters(p->n_cus);
     if (algo == WRNN_ALGO_SPARSE && (!p->sp_nbp || scl < 1)) {
         set_err("block-sparse kernel needs MOL or RAW with 512 classes, >= 256 CUs and GRU matrices with <= 64 surviving 16x1 blocks per block row "
                 "(this pack: mode %s, %d classes, up to %d blocks; device: %d CUs)", p->mode == WRNN_MODE_MOL ? "MOL" : "RAW", p->C, p->sp_max_blocks, p->n_cus);
         return (!p->sp_nbp) ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
     }
-    if (pl->kind == K_CHAIN) {
-        // (planned above)
-    } else if (algo == WRNN_ALGO_SPARSE || (algo == WRNN_ALGO_AUTO && sparse_auto && scl >= 1)) {
-        pl->kind = K_SPARSE; pl->ncl = scl; pl->G = 1;
-        pl->rounds = (groups + scl - 1) / scl;
-        pl->per_round = (B + pl->rounds - 1) / pl->rounds;
-        pl->ngr_max = (pl->per_round + SEG - 1) / SEG;
-        if (pl->ngr_max > scl) { pl->rounds += 1; pl->per_round = (B + pl->rounds - 1) / pl->rounds; pl->ngr_max = (pl->per_round + SEG - 1) / SEG; }
-        int slab = o->slab_steps;
-        if (slab < 1) {
-            slab = p->mode == WRNN_MODE_MOL ? (int)((32u << 20) / ((size_t)pl->per_round * 11 * sizeof(float) * pl->rounds)) : 4096;      // one slab of derived MOL noise
-            if (slab < 16) slab = 16;
-            if (slab > 4096) slab = 4096;
-        }
-        if (slab > T) slab = T;
-        pl->slab = slab;
-        pl->tab_fps = DUO_TAB_FPS;
-    } else if (algo == WRNN_ALGO_AUTO || algo == WRNN_ALGO_LOOP || algo == WRNN_ALGO_DUO || algo == WRNN_ALGO_OCTO) {
-        int ncl = loop_clusters(p->n_cus);
-        if (algo == WRNN_ALGO_OCTO && (p->mode != WRNN_MODE_MOL || octo_clusters(p->n_cus) != MAXCL)) {
-            set_err("wrnn_octo_kernel needs MOL and >= 256 CUs (mode %d, device has %d CUs)", p->mode, p->n_cus);
-            return p->mode != WRNN_MODE_MOL ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
-        }
-        if (algo == WRNN_ALGO_DUO && (!shape_ok || duo_clusters(p->n_cus) < 1)) {
-            set_err("the two-workgroups-per-CU loop kernel needs MOL or RAW with 512 classes, and >= 64 CUs (C = %d, device has %d CUs)", p->C, p->n_cus);
-            return !shape_ok ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
-        }
-        if (shape_ok && ncl >= 1) {
-            if (o->clusters == 1 || o->clusters == 2 || o->clusters == 4) ncl = o->clusters < ncl ? o->clusters : ncl;
-            else if (groups < ncl && !(DUO_AUTO && algo != WRNN_ALGO_LOOP && ncl == MAXCL)) {
-                // no more clusters than groups (rounded up to 1, 2, 4).  Not for the duo kernel: its grid is always 4 clusters (a cluster
-                // without a group leaves at once), so that a small batch sits on whole XCDs exactly as a large one does
-                int c2 = 1; while (c2 < groups) c2 *= 2; if (c2 < ncl) ncl = c2;
-            }
-            const int gmax = algo == WRNN_ALGO_OCTO ? octo_max_depth() : loop_max_depth(p->mode);      // (wrnn_octo_kernel: what its LDS carve holds)
-            int g = o->depth;
-            if (g < 1 || g > gmax) {
-                // as deep as the segments fill evenly: rounds = ceil(groups / (ncl * gmax)), then the shallowest depth that
-                // still needs only that many rounds (deeper pipelines hide the exchange latency; empty slots cost nothing)
-                const int rounds = (groups + ncl * gmax - 1) / (ncl * gmax);
-                g = (groups + ncl * rounds - 1) / (ncl * rounds);
-                if (g < 1) g = 1;
-                if (g > gmax) g = gmax;
-            }
-            pl->kind = K_LOOP; pl->ncl = ncl; pl->G = g;
-            // the two-workgroups-per-CU form (MOL): on request, or when `auto` has >= DUO_MIN_DEPTH groups in flight per cluster
-            // (busy time bounds a step there; with fewer the latency of a slot's chain does, and the duo kernel's chain is one hop longer)
-            if (algo == WRNN_ALGO_DUO || algo == WRNN_ALGO_OCTO || (algo == WRNN_ALGO_AUTO && DUO_AUTO && g >= DUO_MIN_DEPTH && ncl == MAXCL))
-                pl->kind = K_DUO;
-            pl->octo = pl->kind == K_DUO && (algo == WRNN_ALGO_OCTO || (algo == WRNN_ALGO_AUTO && OCTO_AUTO && p->mode == WRNN_MODE_MOL && ncl == MAXCL && !o->clusters));
-            pl->rounds = (groups + ncl * g - 1) / (ncl * g);
-            // balanced rounds of whole segments; every round is cut into <= ncl * g groups of <= 16
-            pl->per_round = (B + pl->rounds - 1) / pl->rounds;
-            pl->ngr_max = (pl->per_round + SEG - 1) / SEG;
-            if (pl->ngr_max > ncl * g) { pl->rounds += 1; pl->per_round = (B + pl->rounds - 1) / pl->rounds; pl->ngr_max = (pl->per_round + SEG - 1) / SEG; }
-            int slab = o->slab_steps;
-            if (slab < 1) {
-                // what a slab holds: wrnn_loop_kernel -- the hoisted conditioning cI (2 KB per segment-step) + the derived MoL noise;
-                // wrnn_duo_kernel forms cI in the loop: only the derived noise (44 B per segment-step)
-                if (pl->kind == K_DUO) slab = p->mode == WRNN_MODE_MOL ? (int)((32u << 20) / ((size_t)pl->per_round * 11 * sizeof(float) * pl->rounds)) : 4096;
-                else slab = (int)((96u << 20) / ((size_t)pl->ngr_max * SEG * H * sizeof(float)));
-                if (slab < 16) slab = 16;
-                if (slab > (pl->kind == K_DUO ? 4096 : 1024)) slab = pl->kind == K_DUO ? 4096 : 1024;
-            }
-            if (slab > T) slab = T;
-            pl->slab = slab;
-            pl->tab_fps = DUO_TAB_FPS;
-        } else if (algo == WRNN_ALGO_LOOP) {
-            set_err("the loop kernel needs >= 64 CUs and (MOL or RAW with 512 classes); device has %d CUs, C=%d", p->n_cus, p->C);
-            return WRNN_ERR_RESIDENCY;
-        }
+    if (algo == WRNN_ALGO_OCTO && (p->mode != WRNN_MODE_MOL || KINDS[K_OCTO].clusters(p->n_cus) != MAXCL)) {
+        set_err("wrnn_octo_kernel needs MOL and >= 256 CUs (mode %d, device has %d CUs)", p->mode, p->n_cus);
+        return p->mode != WRNN_MODE_MOL ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
     }
-    if (pl->kind != K_LOOP && pl->kind != K_DUO && pl->kind != K_SPARSE && pl->kind != K_CHAIN && (pl->t0 != 0 || pl->t1 != T)) {
+    if (algo == WRNN_ALGO_DUO && (!shape_ok || KINDS[K_DUO].clusters(p->n_cus) < 1)) {
+        set_err("the two-workgroups-per-CU loop kernel needs MOL or RAW with 512 classes, and >= 64 CUs (C = %d, device has %d CUs)", p->C, p->n_cus);
+        return !shape_ok ? WRNN_ERR_ARG : WRNN_ERR_RESIDENCY;
+    }
+    if (algo == WRNN_ALGO_LOOP && !(shape_ok && lcl >= 1)) {     // (RESIDENCY for the shape too: as it has always answered)
+        set_err("the loop kernel needs >= 64 CUs and (MOL or RAW with 512 classes); device has %d CUs, C=%d", p->n_cus, p->C);
+        return WRNN_ERR_RESIDENCY;
+    }
+    // ---- the kernel and its clusters
+    const bool sparse_auto = p->sp_nbp && p->mode == WRNN_MODE_MOL;      // (RAW: the sparse kernel's summation order is not the oracle's -- `auto` keeps the dense kernels)
+    Kind kind = K_STREAM;
+    int ncl = 0;
+    if (algo == WRNN_ALGO_CHAIN || (algo == WRNN_ALGO_AUTO && chain_hw && groups <= CHAIN_AUTO_GROUPS && !sparse_auto)) {
+        // one workgroup per CU, one instruction stream per wave.  `auto`: <= 64 segments (one utterance of BASELINE config 2 / 3): one group per 64-CU
+        // cluster, a step is the latency of one chain; <= 128: two groups per cluster
+        kind = K_CHAIN; ncl = ccl;
+    } else if (algo == WRNN_ALGO_SPARSE || (algo == WRNN_ALGO_AUTO && sparse_auto && scl >= 1)) {
+        // (round 5) one group of 16 segments per cluster: the step is the latency of one chain, and sixteen chains run side by side
+        kind = K_SPARSE; ncl = scl;
+    } else if (algo != WRNN_ALGO_STREAM && shape_ok && lcl >= 1) {
+        ncl = lcl;
+        if (o->clusters == 1 || o->clusters == 2 || o->clusters == 4) ncl = o->clusters < ncl ? o->clusters : ncl;
+        else if (groups < ncl && !(DUO_AUTO && algo != WRNN_ALGO_LOOP && ncl == MAXCL)) {
+            // no more clusters than groups (rounded up to 1, 2, 4).  Not for the duo kernel: its grid is always 4 clusters (a cluster
+            // without a group leaves at once), so that a small batch sits on whole XCDs exactly as a large one does
+            int c2 = 1; while (c2 < groups) c2 *= 2; if (c2 < ncl) ncl = c2;
+        }
+        // the two-workgroups-per-CU form: on request, or when `auto` has all four clusters (busy time bounds a step there)
+        kind = K_LOOP;
+        if (algo == WRNN_ALGO_DUO || (algo == WRNN_ALGO_AUTO && DUO_AUTO && ncl == MAXCL)) kind = K_DUO;
+        if (algo == WRNN_ALGO_OCTO || (kind == K_DUO && algo == WRNN_ALGO_AUTO && OCTO_AUTO && p->mode == WRNN_MODE_MOL && !o->clusters)) kind = K_OCTO;
+    }
+    const KindDesc &k = KINDS[kind];
+    pl->kind = kind;
+    if (k.persistent) {
+        plan_split(pl, B, ncl, k.max_depth(p->mode), o->depth);
+        pl->slab = o->slab_steps >= 1 ? o->slab_steps : default_slab(*pl, p->mode);      // (an explicit slab length is taken as given -- short slabs included: tests)
+        if (pl->slab > T) pl->slab = T;
+        pl->tab_fps = DUO_TAB_FPS;
+    } else if (partial) {
         set_err("a partial step range [%d, %d) needs a persistent loop kernel", pl->t0, pl->t1);
         return WRNN_ERR_ARG;
     }
     // the kernels that form their conditioning in the loop index the per-segment, per-slab aux tables with 32-bit byte offsets inside one buffer
     // resource: refused HERE, so that wrnn_plan_segments / wrnn_workspace_bytes_segments report it and nothing has been queued when a call fails
-    if ((pl->kind == K_DUO || pl->kind == K_SPARSE || pl->kind == K_CHAIN) && ((size_t)B * pl->tab_fps + 1) * 3 * H * sizeof(float) >= 0x7FFFF000ull) {
+    if (k.slabbed && ((size_t)B * pl->tab_fps + 1) * 3 * H * sizeof(float) >= 0x7FFFF000ull) {
         set_err("%d segments in one call: the per-slab aux tables exceed a 2 GB buffer resource; split the call (generate_corpus caps a launch at 4096 segments)", B);
         return WRNN_ERR_ARG;
     }
     return WRNN_OK;
 }
 
-WsLayout ws_layout(const wrnn_pack *p, const Plan &pl, int B, int T, int n_frames)
+WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int n_frames)
 {
+    const KindDesc &k = KINDS[pl.kind];
     WsLayout l;
     memset(&l, 0, sizeof l);
     size_t o = 0;
@@ -628,20 +646,17 @@ WsLayout ws_layout(const wrnn_pack *p, const Plan &pl, int B, int T, int n_frame
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
     if (pl.kind == K_GENERIC) { l.total = o; return l; }
-    // per-frame aux tables: one row per frame of the call's conditioning (+ the zero row) -- or, for wrnn_duo_kernel, per SEGMENT and
+    // per-frame aux tables: one row per frame of the call's conditioning (+ the zero row) -- or, for a slabbed kernel, per SEGMENT and
     // slab: (slab - 1) / hop + 2 rows per segment (+ the zero row), refilled for every slab: independent of the corpus' length
-    const bool slabbed = pl.kind == K_DUO || pl.kind == K_SPARSE || pl.kind == K_CHAIN;       // conditioning formed in the loop, per-segment aux tables per slab
-    const size_t tab_rows = slabbed ? (size_t)B * pl.tab_fps + 1 : (size_t)n_frames + 1;
+    const size_t tab_rows = k.slabbed ? (size_t)B * pl.tab_fps + 1 : (size_t)n_frames + 1;
     l.c2f = o;    o = al(o + tab_rows * 3 * H * sizeof(float));
     l.c3f = o;    o = al(o + tab_rows * H * sizeof(float));
     l.c4f = o;    o = al(o + tab_rows * H * sizeof(float));
-    const bool mol = p->mode == WRNN_MODE_MOL;
-    if (pl.kind == K_LOOP || slabbed) {
-        // (the exchange regions a kernel touches: wrnn_chain_kernel G x 4, wrnn_sparse_kernel 16, wrnn_duo_kernel up to 8 x 4 -- its launches may differ in depth)
-        l.xbuf = o;  o = al(o + (pl.kind == K_CHAIN ? chain_xbuf_bytes(pl.G) : pl.kind == K_SPARSE ? sparse_xbuf_bytes() : slabbed ? duo_xbuf_bytes_max() : XBUF_FLOATS * sizeof(float)));
-        l.state = o; o = al(o + (size_t)pl.rounds * (pl.kind == K_SPARSE ? sparse_state_floats() : pl.kind == K_CHAIN ? chain_state_floats(pl.G) : loop_state_floats(pl.G)) * sizeof(float));
-        l.cIf = o;   if (pl.kind == K_LOOP) o = al(o + (size_t)pl.slab * pl.ngr_max * SEG * H * sizeof(float));      // (the duo kernel forms cI in the loop)
-        l.npre = o;  if (mol) o = al(o + (size_t)pl.slab * 11 * B * sizeof(float));      // derived MOL noise of one slab
+    if (k.persistent) {
+        l.xbuf = o;  o = al(o + k.xbuf_bytes(pl.G));
+        l.state = o; o = al(o + (size_t)pl.rounds * k.state_floats(pl.G) * sizeof(float));
+        l.cIf = o;   if (!k.slabbed) o = al(o + (size_t)pl.slab * pl.ngr_max * SEG * H * sizeof(float));      // (a slabbed kernel forms cI in the loop)
+        l.npre = o;  if (p->mode == WRNN_MODE_MOL) o = al(o + (size_t)pl.slab * 11 * B * sizeof(float));      // derived MOL noise of one slab
     } else {
         l.cI = o;    o = al(o + (size_t)T * B * H * sizeof(float));
         l.npre = o;
@@ -696,35 +711,35 @@ int check_segments(int B, int T, const int32_t *seg_pos, const int32_t *seg_lim,
     }
     return WRNN_OK;
 }
+// what wrnn_plan_segments (`out`) and wrnn_workspace_bytes_segments (`ws_bytes`) answer; either may be NULL
+int plan_report(const wrnn_plan_traits *tr, int B, int T, int n_frames, const wrnn_options &o, wrnn_run_info *out, size_t *ws_bytes)
+{
+    Plan pl;
+    const int rc = make_plan(tr, B, T, &o, &pl);
+    if (rc != WRNN_OK) return rc;
+    if (out) {
+        memset(out, 0, sizeof *out);
+        out->kernel = KINDS[pl.kind].name; out->units_per_wg = KINDS[pl.kind].units_per_wg;
+        out->clusters = pl.ncl; out->depth = pl.G; out->rounds = pl.rounds; out->slab_steps = pl.slab;
+    }
+    if (ws_bytes) *ws_bytes = ws_layout(tr, pl, B, T, n_frames).total;
+    return WRNN_OK;
+}
 }  // namespace
 
 extern "C" size_t wrnn_workspace_bytes_segments(const wrnn_pack *p, int32_t n_segments, int32_t T, int32_t n_frames,
                                                 const wrnn_options *opt)
 {
     if (!p || n_segments < 1 || T < 1 || n_frames < 1) return 0;
-    wrnn_options tmp;
-    const wrnn_options *o = norm_options(opt, &tmp);
-    Plan pl;
-    wrnn_options whole = *o;                 // the workspace of a partial-range call is the whole call's
-    whole.t_begin = 0; whole.t_end = 0;
-    if (make_plan(p, n_segments, T, &whole, &pl) != WRNN_OK) return 0;
-    return ws_layout(p, pl, n_segments, T, n_frames).total;
+    size_t bytes = 0;
+    (void)plan_report(&p->tr, n_segments, T, n_frames, whole_call(opt), nullptr, &bytes);
+    return bytes;
 }
 
 extern "C" int wrnn_plan_segments(const wrnn_pack *p, int32_t n_segments, int32_t T, const wrnn_options *opt, wrnn_run_info *out)
 {
     if (!p || !out || n_segments < 1 || T < 1) { set_err("bad argument"); return WRNN_ERR_ARG; }
-    wrnn_options tmp;
-    wrnn_options whole = *norm_options(opt, &tmp);
-    whole.t_begin = 0; whole.t_end = 0;
-    Plan pl;
-    int rc = make_plan(p, n_segments, T, &whole, &pl);
-    if (rc != WRNN_OK) return rc;
-    memset(out, 0, sizeof *out);
-    out->kernel = pl.kind == K_GENERIC ? "wrnn_generic_kernel" : pl.kind == K_CHAIN ? "wrnn_chain_kernel" : pl.kind == K_DUO ? (pl.octo ? "wrnn_octo_kernel" : "wrnn_duo_kernel") : pl.kind == K_LOOP ? "wrnn_loop_kernel" : (pl.kind == K_SPARSE ? "wrnn_sparse_kernel" : "wrnn_stream_kernel");
-    out->units_per_wg = pl.kind == K_STREAM ? 0 : (pl.kind == K_SPARSE ? 64 : 16);
-    out->clusters = pl.ncl; out->depth = pl.G; out->rounds = pl.rounds; out->slab_steps = pl.slab;
-    return WRNN_OK;
+    return plan_report(&p->tr, n_segments, T, 1, whole_call(opt), out, nullptr);
 }
 
 extern "C" size_t wrnn_workspace_bytes(const wrnn_pack *p, const wrnn_geometry *g, const wrnn_options *opt)
@@ -741,19 +756,11 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     if (!p || !mels_up || !aux || !noise || !out || !workspace) { set_err("NULL argument"); return WRNN_ERR_ARG; }
     int rc = check_segments(B, T, seg_pos, seg_lim, L, hop, n_frames);
     if (rc != WRNN_OK) return rc;
-    wrnn_options tmp;
-    const wrnn_options *o = norm_options(opt, &tmp);
-    Plan pl;
-    {   // plan for the WHOLE call (a continuation must land on the same split and workspace layout)
-        wrnn_options whole = *o;
-        whole.t_begin = 0; whole.t_end = 0;
-        if ((rc = make_plan(p, B, T, &whole, &pl)) != WRNN_OK) return rc;
-        pl.t0 = o->t_begin; pl.t1 = o->t_end;
-        if (pl.t0 == 0 && pl.t1 == 0) pl.t1 = T;
-        if (pl.t0 < 0 || pl.t1 > T || pl.t0 >= pl.t1) { set_err("bad step range [%d, %d) of T=%d", pl.t0, pl.t1, T); return WRNN_ERR_ARG; }
-        if (pl.kind != K_LOOP && pl.kind != K_DUO && pl.kind != K_SPARSE && pl.kind != K_CHAIN && (pl.t0 != 0 || pl.t1 != T)) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
-    }
-    const WsLayout l = ws_layout(p, pl, B, T, n_frames);
+    const wrnn_options opts = norm_struct(opt), *o = &opts;
+    Plan pl;      // (kernel, split and workspace layout do not depend on the step range: a continuation lands on the whole call's)
+    if ((rc = make_plan(&p->tr, B, T, o, &pl)) != WRNN_OK) return rc;
+    const KindDesc &k = KINDS[pl.kind];
+    const WsLayout l = ws_layout(&p->tr, pl, B, T, n_frames);
     if (workspace_bytes < l.total) { set_err("workspace %zu < required %zu", workspace_bytes, l.total); return WRNN_ERR_WORKSPACE; }
     if (((uintptr_t)workspace & 255) != 0) { set_err("workspace must be 256-byte aligned"); return WRNN_ERR_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
@@ -773,7 +780,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     if (o->mel_stage) {
         // the last up-sampling stage inside the loop: `mels_up` is that stage's input.  Everything is checked here, on the host: the
         // kernel reads rows j / s - 1 .. j / s + 1 without a bound.
-        if (pl.kind != K_DUO && pl.kind != K_SPARSE && pl.kind != K_CHAIN) { set_err("wrnn_options.mel_stage: only wrnn_duo_kernel / wrnn_sparse_kernel / wrnn_chain_kernel form the last up-sampling stage (this call runs on another kernel)"); return WRNN_ERR_ARG; }
+        if (!k.mel_stage) { set_err("wrnn_options.mel_stage: only wrnn_duo_kernel / wrnn_sparse_kernel / wrnn_chain_kernel form the last up-sampling stage (this call runs on another kernel)"); return WRNN_ERR_ARG; }
         if (o->mel_stage != 1 || o->mel_scale != LAST_SCALE || !o->mel_taps || !o->seg_moff || o->mel_rows < 3) {
             set_err("wrnn_options.mel_stage=%d: needs mel_scale == %d (got %d), mel_taps, seg_moff, mel_rows >= 3", o->mel_stage, LAST_SCALE, o->mel_scale);
             return WRNN_ERR_ARG;
@@ -809,13 +816,13 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         g.fc1T = p->g_fc1T; g.fc1_b = p->fc1_b; g.fc2T = p->g_fc2T; g.fc2_b = p->fc2_b; g.fc3T = p->fc3T; g.fc3_b = p->fc3_b;
         g.mels_up = mels_up; g.aux = aux; g.noise = noise; g.force_x = o->force_x; g.out = out; g.dbg_logits = o->logits;
         g.seg_pos = d_pos; g.seg_lim = d_lim;
-        g.H = p->gH; g.F = p->gF; g.M = p->gM; g.A = p->gA; g.C = p->C; g.B = B; g.T = T; g.hop = hop;
+        g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-        HIPCHK(launch_generic(g, p->mode, stream));
+        HIPCHK(launch_generic(g, p->tr.mode, stream));
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         wrnn_run_info gi;
         memset(&gi, 0, sizeof gi);
-        gi.kernel = "wrnn_generic_kernel"; gi.rounds = 1; gi.slab_steps = T; gi.launches = 1;
+        gi.kernel = k.name; gi.rounds = 1; gi.slab_steps = T; gi.launches = 1;
         if (o->info) *o->info = gi;
         return enqueue_progress(o, T, T, B, stream);
     }
@@ -827,8 +834,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     c.c2f = (float *)(ws + l.c2f); c.c3f = (float *)(ws + l.c3f); c.c4f = (float *)(ws + l.c4f);
     c.seg_pos = d_pos; c.seg_lim = d_lim;
     c.B = B; c.T = T; c.hop = hop; c.NF = n_frames;
-    const bool slabbed = pl.kind == K_DUO || pl.kind == K_SPARSE || pl.kind == K_CHAIN;
-    if (slabbed) {
+    if (k.slabbed) {
         // the aux tables are per segment and slab (filled in the slab loop): a slab may not span more than tab_fps - 2 whole hops
         const long eff = (long)(pl.tab_fps - 2) * hop + 1;
         if (pl.slab > eff) pl.slab = (int)eff;
@@ -847,7 +853,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     a.prof = (u64 *)o->phase_clocks;
     a.tuning = o->tuning;
     a.seg_pos = d_pos; a.seg_lim = d_lim;
-    a.Btot = B; a.T = T; a.hop = hop; a.NF = n_frames; a.C = p->C;
+    a.Btot = B; a.T = T; a.hop = hop; a.NF = n_frames; a.C = p->tr.C;
     a.NG = (B + SEG - 1) / SEG;
     a.Nall = B;
     a.xcc_tab = (unsigned *)(ws + l.xcc);
@@ -857,16 +863,14 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
 
     wrnn_run_info info;
     memset(&info, 0, sizeof info);
+    info.kernel = k.name; info.units_per_wg = k.units_per_wg;
     info.clusters = pl.ncl; info.depth = pl.G; info.rounds = pl.rounds; info.slab_steps = pl.slab;
 
-    if (pl.kind == K_LOOP || slabbed) {
+    if (k.persistent) {
         // ---- persistent loop kernels: for every slab of steps { derived noise; for every round { conditioning slab; loop } } ----
-        const bool duo = slabbed, sparse = pl.kind == K_SPARSE, chain = pl.kind == K_CHAIN;      // (duo: the conditioning is formed in the loop)
-        const bool octo = pl.kind == K_DUO && pl.octo;
-        info.kernel = chain ? "wrnn_chain_kernel" : sparse ? "wrnn_sparse_kernel" : (duo ? (octo ? "wrnn_octo_kernel" : "wrnn_duo_kernel") : "wrnn_loop_kernel"); info.units_per_wg = sparse ? 64 : 16;
         a.sp_vals = p->sp_vals; a.sp_cols = p->sp_cols;
         a.sp_fc_vals = (o->tuning & 2048) ? nullptr : p->sp_fc_vals; a.sp_fc_cols = p->sp_fc_cols;      // (tuning bit 11: dense fc stages on a pack whose Linear layers are sparse too -- A/B)
-        const bool mol = p->mode == WRNN_MODE_MOL;
+        const bool mol = p->tr.mode == WRNN_MODE_MOL;
         a.xbuf = (float *)(ws + l.xbuf);
         a.cIf = (const float *)(ws + l.cIf);
         a.G = pl.G;
@@ -874,13 +878,13 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         for (int s0 = pl.t0; s0 < pl.t1; s0 += pl.slab) {
             const int s1 = s0 + pl.slab < pl.t1 ? s0 + pl.slab : pl.t1;
             if (mol) {   // noise rows are relative to t_begin (wrnn_options.t_begin)
-                HIPCHK(launch_noise_mol(noise + (size_t)(s0 - pl.t0) * 11 * B, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->n_cus, stream));
+                HIPCHK(launch_noise_mol(noise + (size_t)(s0 - pl.t0) * 11 * B, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->tr.n_cus, stream));
                 a.noise_pre = (const float *)(ws + l.npre);
                 a.noise_t0 = s0;
             } else {
                 a.noise_t0 = pl.t0;
             }
-            if (duo) {   // this slab's aux tables of every segment of the call
+            if (k.slabbed) {   // this slab's aux tables of every segment of the call
                 c.t0 = s0; c.B = B; c.FPS = pl.tab_fps;
                 HIPCHK(launch_cond_frames_slab(c, stream));
                 a.tab_fps = pl.tab_fps; a.tab_t0 = s0;
@@ -891,18 +895,17 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
                 if (nr < 1) continue;
                 const int ngr = (nr + SEG - 1) / SEG;
                 c.t0 = s0; c.t1 = s1; c.rb0 = rb0; c.B = nr; c.NG = ngr;
-                if (!duo) HIPCHK(launch_cond_frag(c, p->n_cus, stream));
-                // every word of the exchange ring = the sentinel.  The duo kernel leaves its ring consistent at the end of a launch
+                if (!k.slabbed) HIPCHK(launch_cond_frag(c, p->tr.n_cus, stream));
+                // every word of the exchange ring = the sentinel.  A slabbed kernel leaves its ring consistent at the end of a launch
                 // (every step re-arms the entries it will write two or three steps later), so it needs the fill only where a round starts: the first
                 // launch of a call that starts at step 0, or any launch when several rounds share the buffer
-                if (!duo) HIPCHK(hipMemsetAsync(ws + l.xbuf, 0xFF, XBUF_FLOATS * sizeof(float), stream));
-                else if (s0 == 0 || pl.rounds > 1 || (o->tuning & 4)) HIPCHK(hipMemsetAsync(ws + l.xbuf, 0xFF, chain ? chain_xbuf_bytes(pl.G) : sparse ? sparse_xbuf_bytes() : duo_xbuf_bytes(pl.G), stream));
-                if (duo) HIPCHK(hipMemsetAsync(ws + l.xcc, 0, XCC_WORDS * sizeof(unsigned), stream));      // placement handshake of this launch
-                a.state = (float *)(ws + l.state) + (size_t)r * (sparse ? sparse_state_floats() : chain ? chain_state_floats(pl.G) : loop_state_floats(pl.G));
+                if (!k.slabbed || s0 == 0 || pl.rounds > 1 || (o->tuning & 4)) HIPCHK(hipMemsetAsync(ws + l.xbuf, 0xFF, k.xbuf_fill(pl.G), stream));
+                if (k.slabbed) HIPCHK(hipMemsetAsync(ws + l.xcc, 0, XCC_WORDS * sizeof(unsigned), stream));      // placement handshake of this launch
+                a.state = (float *)(ws + l.state) + (size_t)r * k.state_floats(pl.G);
                 a.t0 = s0; a.t1 = s1; a.cI_t0 = s0; a.rb0 = rb0; a.Btot = nr; a.NG = ngr; a.resume = s0 > 0 ? 1 : 0;
-                a.kind_tag = chain ? 4 : sparse ? 3 : (duo ? (octo ? 5 : 2) : 1);
+                a.kind_tag = k.kind_tag;
                 if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-                hipError_t e = chain ? launch_chain(a, p->mode, stream) : sparse ? launch_sparse(a, p->sp_nbp, p->mode, stream) : (duo ? (octo ? launch_octo(a, pl.ncl, p->mode, stream) : launch_duo(a, pl.ncl, p->mode, stream)) : launch_loop(a, pl.ncl, p->mode, stream));
+                hipError_t e = k.launch(a, pl.ncl, p->tr.sp_nbp, p->tr.mode, stream);
                 // (two workgroups per CU not co-resident right now: WRNN_ERR_RESIDENCY -- the caller re-plans with WRNN_ALGO_LOOP, whose
                 // workspace layout is another one: wavernn_amd/engine.py does)
                 if (e != hipSuccess) {
@@ -919,12 +922,11 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         // ---- stream kernel: whole-T conditioning in [t][segment][H] order, one launch --------------------
         c.cI = (float *)(ws + l.cI);
         a.cI = c.cI;
-        HIPCHK(launch_cond(c, p->n_cus, o->cond_valu != 0, stream));
-        info.kernel = "wrnn_stream_kernel";
+        HIPCHK(launch_cond(c, p->tr.n_cus, o->cond_valu != 0, stream));
         a.b0 = 0;
         a.nb = B;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-        HIPCHK(launch_stream(a, p->mode, stream));
+        HIPCHK(launch_stream(a, p->tr.mode, stream));
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         info.launches = 1;
         if ((rc = enqueue_progress(o, T, T, B, stream)) != WRNN_OK) return rc;
@@ -964,17 +966,15 @@ extern "C" int wrnn_debug_read_exchange(const wrnn_pack *p, void *workspace, int
                                         const wrnn_options *opt, int cluster, int slot, int layer, int ring, float *host_out)
 {
     if (!p || !workspace || !host_out) { set_err("NULL argument"); return WRNN_ERR_ARG; }
-    wrnn_options tmp;
-    wrnn_options whole = *norm_options(opt, &tmp);
-    whole.t_begin = 0; whole.t_end = 0;
+    const wrnn_options whole = whole_call(opt);
     Plan pl;
-    int rc = make_plan(p, n_segments, T, &whole, &pl);
+    int rc = make_plan(&p->tr, n_segments, T, &whole, &pl);
     if (rc != WRNN_OK) return rc;
     if (pl.kind != K_LOOP || cluster < 0 || cluster >= MAXCL || slot < 0 || slot >= LMAXG || layer < 0 || layer >= NXLAYER || ring < 0 || ring >= XRING) {
         set_err("no such exchange layer");
         return WRNN_ERR_ARG;
     }
-    const WsLayout l = ws_layout(p, pl, n_segments, T, n_frames);
+    const WsLayout l = ws_layout(&p->tr, pl, n_segments, T, n_frames);
     HIPCHK(hipDeviceSynchronize());
     std::vector<float> frag((size_t)SEG * H);
     const size_t off = ((((size_t)cluster * LMAXG + slot) * NXLAYER + layer) * XRING + ring) * SEG * H;
@@ -985,6 +985,17 @@ extern "C" int wrnn_debug_read_exchange(const wrnn_pack *p, void *workspace, int
             host_out[(size_t)j * H + k] = frag[(size_t)(((w * 8 + r) * 64 + kq * 16 + j) * 4 + e)];
         }
     return WRNN_OK;
+}
+
+// Test hook: the launch planner on a description of pack and device -- make_plan + ws_layout, as wrnn_plan_segments and
+// wrnn_workspace_bytes_segments run them on a pack's own traits -- without a pack, a device or the HIP runtime.
+extern "C" int wrnn_debug_plan(const wrnn_plan_traits *traits, int32_t n_segments, int32_t T, int32_t n_frames,
+                               const wrnn_options *opt, wrnn_run_info *out, size_t *workspace_bytes)
+{
+    if (!traits || !out || !workspace_bytes || n_segments < 1 || T < 1 || n_frames < 1) { set_err("bad argument"); return WRNN_ERR_ARG; }
+    *workspace_bytes = 0;
+    const wrnn_plan_traits tr = norm_struct(traits);
+    return plan_report(&tr, n_segments, T, n_frames, norm_struct(opt), out, workspace_bytes);      // (the step range stays: validated as for wrnn_generate_segments)
 }
 
 static float g_selftest_metric = -1.f;

@@ -43,6 +43,16 @@ constexpr int STATUS_WORDS = 16;    // 0 abort flag, 1 code, 2 wg, 3 step, 4 det
 constexpr int XCC_WORDS = MAXCL * 128; // wrnn_duo.hip placement handshake
 constexpr int MAXWG = 256;    // workgroups of a persistent launch
 
+// Host side: the clusters of 64 CUs a device hosts for wrnn_loop_kernel / wrnn_duo_kernel / wrnn_octo_kernel (64 workgroups of one, 128 of two per CU,
+// or 64 of 512 threads): 1, 2 or 4
+inline int clusters_of_64(int n_cus)
+{
+    int ncl = n_cus / 64;
+    if (ncl > MAXCL) ncl = MAXCL;
+    while (ncl > 1 && (8 % ncl) != 0) --ncl;
+    return ncl;
+}
+
 // Everything the loop kernels read.  All pointers are device pointers.
 struct LoopArgs {
     // raw row-major weights (persistent kernel gathers its MFMA A-fragments from these once)

@@ -1166,15 +1166,6 @@ size_t duo_xbuf_bytes(int G) { return (size_t)G * MAXCL * DNX * DLAYER_ENTRIES *
 size_t duo_xbuf_bytes_max() { return DXBUF_FLOATS * sizeof(float); }
 int duo_max_depth() { return LMAXG; }
 
-// clusters this device can host at two workgroups per CU (64 CUs per cluster, as wrnn_loop_kernel)
-int duo_clusters(int n_cus)
-{
-    int ncl = n_cus / LNWGC;
-    if (ncl > MAXCL) ncl = MAXCL;
-    while (ncl > 1 && (8 % ncl) != 0) --ncl;
-    return ncl;
-}
-
 // How the ih workgroups get a stage's operand (round 6, profiles/r06l_*: us per step at 1 / 2 / 3 / 4 / 8 slots in flight -- register loads
 // behind the back half 12.3 / 16.4 / 19.4 / 22.7 / 41.3, LDS prefetch one stage ahead 12.4 / 16.6 / 19.7 / 23.6 / 38.3): the prefetch pays
 // once a step is the workgroups' busy time, not the latency of a slot's chain (its 8 LDS-DMA issues and the read-back cost what the exposed

@@ -728,14 +728,6 @@ int loop_max_depth(int mode)
 
 size_t loop_state_floats(int G) { return (size_t)MAXCL * LNWGC * G * LGRP; }
 
-int loop_clusters(int n_cus)
-{
-    int ncl = n_cus / LNWGC;
-    if (ncl > MAXCL) ncl = MAXCL;
-    while (ncl > 1 && (8 % ncl) != 0) --ncl;
-    return ncl;
-}
-
 // One cooperative launch: clusters x 64 workgroups; args.G groups in flight per cluster, steps [args.t0, args.t1).
 hipError_t launch_loop(const LoopArgs &args, int ncl, int mode, hipStream_t stream)
 {

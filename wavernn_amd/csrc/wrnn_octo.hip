@@ -807,14 +807,6 @@ size_t octo_lds_bytes(int G) { return (size_t)octo_lds(G).total * sizeof(float);
 constexpr int OMAXG = 4;                     // slots in flight per cluster: 8.3 KB of LDS per slot beside 114 KB of operand blocks, partial tiles and the fc tile
 static_assert(sizeof(float) * (size_t)octo_lds(OMAXG).total <= 160 * 1024, "LDS carve");
 int octo_max_depth() { return OMAXG; }
-// clusters this device can host at one 512-thread workgroup per CU (64 CUs per cluster)
-int octo_clusters(int n_cus)
-{
-    int ncl = n_cus / LNWGC;
-    if (ncl > MAXCL) ncl = MAXCL;
-    while (ncl > 1 && (8 % ncl) != 0) --ncl;
-    return ncl;
-}
 
 hipError_t launch_octo(const LoopArgs &args, int ncl, int mode, hipStream_t stream)
 {
