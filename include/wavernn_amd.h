@@ -342,9 +342,11 @@ int wrnn_post_unfold(const float *segments, int32_t T, int32_t n_utt, const int3
 const char *wrnn_post_last_error(void);
 
 /*
- * BASELINE config 3's caller: the Tacotron decoder loop as one persistent kernel (on hardware since round 3:
- * tests/test_gpu_config3.py compares it with the reference's own output, tests/golden/tacotron_decoder_200f.npz).  Replaces the per-frame loop of `Tacotron.generate()` (reference models/tacotron.py:396-414) around
- * `Decoder.forward` (:218-279) for one sentence; the encoder (:24-39, once per sentence) and the post-net stay with the caller.
+ * BASELINE config 3's caller, the Tacotron side (ids -> mel -> linear), in three steps: wrnn_taco_encode (embedding, encoder pre-net, encoder CBHG,
+ * `encoder_proj`: reference models/tacotron.py:24-39, :403-404; once per sentence), wrnn_taco_decode (the decoder loop as one persistent
+ * kernel, SURVEY.md section 8 row f3: it replaces the per-frame loop of `Tacotron.generate()`, :396-414, around `Decoder.forward`, :218-279;
+ * on hardware since round 3, tests/test_gpu_config3.py compares it with the reference's own output, tests/golden/tacotron_decoder_200f.npz)
+ * and wrnn_taco_postnet (the post-net CBHG and `post_proj`, :424-425).  The first and the last are declared further down (wrnn_taco_front).
  * All pointers are DEVICE pointers to contiguous float32 tensors in the reference's state-dict layouts (`decoder.*`).
  */
 typedef struct wrnn_taco_weights {
@@ -398,6 +400,61 @@ typedef struct wrnn_bigru_call {
     void *stream;
 } wrnn_bigru_call;
 int wrnn_bigru(int device, const wrnn_bigru_call *c);
+
+/*
+ * The rest of Tacotron inference around the decoder loop (csrc/wrnn_cbhg.hip): the embedding and the encoder pre-net, both CBHGs (reference
+ * models/tacotron.py:57-139: conv bank of BatchNormConv :43-54, max-pool, two projections, residual, pre_highway, highways, the
+ * bidirectional GRU through wrnn_bigru), `encoder_proj` and `post_proj`.  float32 throughout (f32 MFMA).  The weight pointers are DEVICE
+ * pointers to contiguous float32 tensors in the reference's state-dict layouts; create copies and repacks them (they may be freed after it).
+ * Supported: conv banks of 1..16, channel counts that are multiples of 16 (16..4096), highway / GRU width 128; anything else is
+ * WRNN_ERR_ARG with a message.  Errors: wrnn_taco_last_error().
+ */
+typedef struct wrnn_cbhg_weights {
+    int32_t K;                            /* conv bank size: widths 1..K (encoder 16, post-net 8) */
+    int32_t in_channels;                  /* encoder 128, post-net 80 (n_mels) */
+    int32_t proj1_channels;               /* conv_project1 outputs: 128 / 256 */
+    int32_t proj2_channels;               /* conv_project2 outputs: 128 / 80; == in_channels (the residual) */
+    int32_t channels;                     /* bank outputs per width, highway and GRU width: 128 */
+    int32_t num_highways;                 /* 0..4 */
+    const float *bank_conv_w[16];         /* conv1d_bank.{i}.conv.weight (channels, in_channels, i + 1) */
+    const float *bank_bn_w[16], *bank_bn_b[16], *bank_bn_mean[16], *bank_bn_var[16];   /* conv1d_bank.{i}.bnorm.{weight,bias,running_mean,running_var} */
+    const float *proj1_conv_w;            /* conv_project1.conv.weight (proj1_channels, K * channels, 3) */
+    const float *proj1_bn_w, *proj1_bn_b, *proj1_bn_mean, *proj1_bn_var;
+    const float *proj2_conv_w;            /* conv_project2.conv.weight (proj2_channels, proj1_channels, 3) */
+    const float *proj2_bn_w, *proj2_bn_b, *proj2_bn_mean, *proj2_bn_var;
+    const float *pre_highway_w;           /* pre_highway.weight (channels, proj2_channels); NULL exactly when proj2_channels == channels */
+    const float *highway_w1[4], *highway_b1[4], *highway_w2[4], *highway_b2[4];        /* highways.{i}.{W1,W2}.{weight,bias} */
+    const float *rnn_w_ih, *rnn_w_hh, *rnn_b_ih, *rnn_b_hh;                             /* rnn.{weight,bias}_{ih,hh}_l0: [384][128] x2, [384] x2 */
+    const float *rnn_w_ih_rev, *rnn_w_hh_rev, *rnn_b_ih_rev, *rnn_b_hh_rev;             /* ..._l0_reverse */
+} wrnn_cbhg_weights;
+
+typedef struct wrnn_taco_front_weights {
+    uint32_t struct_bytes;
+    int32_t n_symbols, embed_dims;        /* encoder.embedding.weight (n_symbols, embed_dims): 148 x 256 */
+    int32_t prenet1, prenet2;             /* encoder.pre_net.fc1 / fc2 outputs: 256 / 128 */
+    int32_t encoder_proj_dims;            /* encoder_proj.weight (encoder_proj_dims, 2 channels): 256 */
+    int32_t n_mels, fft_bins;             /* post_proj.weight (fft_bins, 2 channels): 80 / 80 */
+    const float *embedding;
+    const float *prenet_fc1_w, *prenet_fc1_b, *prenet_fc2_w, *prenet_fc2_b;
+    const float *encoder_proj_w, *post_proj_w;
+    wrnn_cbhg_weights encoder_cbhg;       /* encoder.cbhg.* */
+    wrnn_cbhg_weights postnet;            /* postnet.* */
+} wrnn_taco_front_weights;
+typedef struct wrnn_taco_front wrnn_taco_front;     /* opaque and immutable: the repacked weights and the BatchNorm scale / shift pairs */
+
+int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int device, wrnn_taco_front **out);
+void wrnn_taco_front_destroy(wrnn_taco_front *f);
+/* bytes of caller-owned, 256-byte aligned workspace one call with this many rows (characters / frames) needs */
+size_t wrnn_taco_front_workspace_bytes(const wrnn_taco_front *f, int32_t rows);
+/* ids: device int32 [n] -> seq_out device [n][2 channels] (encoder_seq, :403), seq_proj_out device [n][encoder_proj_dims] (:404): what
+ * wrnn_taco_call.seq / seq_proj take.  pre_rnn_out: NULL, or device [n][channels] that receives the highway output in front of the GRU
+ * (a test hook).  Outputs 16-byte aligned.  Asynchronous on `stream`; no allocation, no synchronisation. */
+int wrnn_taco_encode(const wrnn_taco_front *f, const int32_t *ids, int32_t n, float *seq_out, float *seq_proj_out, float *pre_rnn_out,
+                     void *workspace, size_t workspace_bytes, void *stream);
+/* mel: device [n_mels][N] (the decoder's frames, (n_mels, N) as `Tacotron.generate()` holds them) -> linear_out device [N][fft_bins]
+ * (the reference returns its transpose; the vocoder takes it).  pre_rnn_out as above, [N][channels]. */
+int wrnn_taco_postnet(const wrnn_taco_front *f, const float *mel, int32_t N, float *linear_out, float *pre_rnn_out,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* Self tests of the device primitives (MFMA fragment layout, inter-workgroup granule all-gather).
  * Synchronous.  WRNN_OK or an error with a message. */

@@ -12,6 +12,8 @@ CSRC = os.path.join(_HERE, 'csrc')
 SO_PATH = os.path.join(CSRC, 'libwavernn_amd.so')
 
 WRNN_OK = 0
+ERR_ARG = -1                # WRNN_ERR_ARG: bad argument / unsupported dims
+ERR_NO_DEVICE = -2          # WRNN_ERR_NO_DEVICE
 ERR_RESIDENCY = -6          # WRNN_ERR_RESIDENCY: the persistent grid cannot be co-resident on this device
 MODE_RAW, MODE_MOL = 0, 1
 ABI_VERSION = 9
@@ -25,7 +27,8 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
-           'wrnn_taco_last_error', 'wrnn_bigru']
+           'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
+           'wrnn_taco_encode', 'wrnn_taco_postnet']
 
 
 class Weights(ctypes.Structure):
@@ -65,6 +68,26 @@ class BigruCall(ctypes.Structure):
     """wrnn_bigru_call."""
     _fields_ = [('struct_bytes', ctypes.c_uint32), ('T', ctypes.c_int32), ('hidden', ctypes.c_int32)] + \
                [(n, ctypes.c_void_p) for n in ('gi_fwd', 'gi_rev', 'w_hh_fwd', 'w_hh_rev', 'b_hh_fwd', 'b_hh_rev', 'out', 'stream')]
+
+
+class CbhgWeights(ctypes.Structure):
+    """wrnn_cbhg_weights: one CBHG's tensors (device pointers, the reference's state-dict layouts)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('K', 'in_channels', 'proj1_channels', 'proj2_channels', 'channels', 'num_highways')] + \
+               [(n, ctypes.c_void_p * 16) for n in ('bank_conv_w', 'bank_bn_w', 'bank_bn_b', 'bank_bn_mean', 'bank_bn_var')] + \
+               [(n, ctypes.c_void_p) for n in ('proj1_conv_w', 'proj1_bn_w', 'proj1_bn_b', 'proj1_bn_mean', 'proj1_bn_var', 'proj2_conv_w',
+                                               'proj2_bn_w', 'proj2_bn_b', 'proj2_bn_mean', 'proj2_bn_var', 'pre_highway_w')] + \
+               [(n, ctypes.c_void_p * 4) for n in ('highway_w1', 'highway_b1', 'highway_w2', 'highway_b2')] + \
+               [(n, ctypes.c_void_p) for n in ('rnn_w_ih', 'rnn_w_hh', 'rnn_b_ih', 'rnn_b_hh', 'rnn_w_ih_rev', 'rnn_w_hh_rev', 'rnn_b_ih_rev',
+                                               'rnn_b_hh_rev')]
+
+
+class TacoFrontWeights(ctypes.Structure):
+    """wrnn_taco_front_weights (wrnn_taco_front_create)."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ('n_symbols', 'embed_dims', 'prenet1', 'prenet2', 'encoder_proj_dims', 'n_mels', 'fft_bins')] + \
+               [(n, ctypes.c_void_p) for n in ('embedding', 'prenet_fc1_w', 'prenet_fc1_b', 'prenet_fc2_w', 'prenet_fc2_b', 'encoder_proj_w',
+                                               'post_proj_w')] + \
+               [('encoder_cbhg', CbhgWeights), ('postnet', CbhgWeights)]
 
 
 class Geometry(ctypes.Structure):
@@ -194,6 +217,15 @@ def lib():
     L.wrnn_taco_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32 * 4), ctypes.c_void_p]
     L.wrnn_taco_last_error.restype = ctypes.c_char_p
     L.wrnn_bigru.argtypes = [ctypes.c_int, ctypes.POINTER(BigruCall)]
+    L.wrnn_taco_front_create.argtypes = [ctypes.POINTER(TacoFrontWeights), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    L.wrnn_taco_front_destroy.argtypes = [ctypes.c_void_p]
+    L.wrnn_taco_front_destroy.restype = None
+    L.wrnn_taco_front_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    L.wrnn_taco_front_workspace_bytes.restype = ctypes.c_size_t
+    L.wrnn_taco_encode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.wrnn_taco_postnet.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_size_t, ctypes.c_void_p]
     L.wrnn_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.wrnn_selftest.argtypes = [ctypes.c_int, ctypes.c_int]
     L.wrnn_selftest_metric.restype = ctypes.c_float

@@ -754,7 +754,7 @@ __global__ __launch_bounds__(GR_NT, 1) void wrnn_bigru_kernel(const BigruArgs a)
 using namespace wrnn;
 
 static thread_local char g_taco_err[400] = "";
-static void taco_err(const char *fmt, ...)
+void taco_err(const char *fmt, ...)                 // (also the message buffer of wrnn_cbhg.hip)
 {
     va_list ap;
     va_start(ap, fmt);

@@ -32,6 +32,7 @@ def main(argv=None):
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--steps', type=int, default=2000, help='decoder step limit (Tacotron.generate default)')
     ap.add_argument('--output', default='.', help='output directory')
+    ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet)')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -52,7 +53,7 @@ def main(argv=None):
     for i, text in enumerate(texts, 1):
         print(f'\n| Generating {i}/{len(texts)}')
         t0 = time.perf_counter()
-        _, mel, _ = tts.generate(text_to_ids(text), steps=a.steps, kernel=True)   # the POSTNET output (:142)
+        _, mel, _ = tts.generate(text_to_ids(text), steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel)   # the POSTNET output (:142)
         t1 = time.perf_counter()
         m = torch.tensor(tacotron_to_wavernn_mel(mel)).unsqueeze(0)
         name = f'__input_{text[:10]}_{v_type}_{tts_k}k.wav' if a.input_text else f'{i}_{v_type}_{tts_k}k.wav'

@@ -8,7 +8,9 @@ are identities in `generate()`, which calls `self.eval()` first, :371).  On the 
 (tests/test_tacotron_mirror.py, build container; tests/golden/tacotron_decoder_200f.npz holds the reference's own output for the
 GPU tests' weights); on the GPU the decoder loop -- one sentence = one serial chain of ~40 small ops per mel frame -- runs as ONE
 persistent kernel (`generate(..., kernel=True)`: `wrnn_taco_decode`, csrc/wrnn_taco.hip) and the CBHGs'
-bidirectional GRUs as `wrnn_bigru`; the eager loop stays as the any-device form.
+bidirectional GRUs as `wrnn_bigru`; the eager loop stays as the any-device form.  `generate(..., cbhg_kernel=True)` (opt-in) also runs
+the encoder and the post-net -- embedding, pre-net, both CBHGs, `encoder_proj`, `post_proj` -- as HIP kernels through the C ABI
+(`wrnn_taco_encode` / `wrnn_taco_postnet`, csrc/wrnn_cbhg.hip), so that the whole Tacotron side is behind include/wavernn_amd.h.
 
     tts = TacotronInference(state_dict, device='cuda')
     _, m, attn = tts.generate(ids, steps=800)                 # same returns as the reference: (80, N), (fft, N), (N, chars); the
@@ -50,6 +52,9 @@ class TacotronInference:
         self.stop_threshold = float(p['stop_threshold'].item()) if 'stop_threshold' in p else -3.4
         self._enc_k = self._count('encoder.cbhg.conv1d_bank.%d.conv.weight')
         self._post_k = self._count('postnet.conv1d_bank.%d.conv.weight')
+        self.last_front_path = None                # 'hip' / 'torch': what the last generate() ran the encoder and the post-net on
+        self._front = None                         # wrnn_taco_front handle (one per instance), False: create refused the dims
+        self._front_ws = None                      # its workspace, reused and grown
 
     def _count(self, pattern):
         n = 0
@@ -72,8 +77,8 @@ class TacotronInference:
         x = F.relu(F.linear(x, self.p[prefix + '.fc1.weight'], self.p[prefix + '.fc1.bias']))
         return F.relu(F.linear(x, self.p[prefix + '.fc2.weight'], self.p[prefix + '.fc2.bias']))
 
-    def _cbhg(self, x, prefix, K):
-        """CBHG (:57-139): conv bank 1..K -> max pool -> two projections -> residual -> highways -> bidirectional GRU."""
+    def _cbhg_front(self, x, prefix, K):
+        """CBHG (:57-139) in front of its GRU: conv bank 1..K -> max pool -> two projections -> residual -> highways.  (1, n, channels)."""
         p = self.p
         n = x.size(-1)
         res = x
@@ -91,6 +96,12 @@ class TacotronInference:
             g = torch.sigmoid(F.linear(x, p[q + 'W2.weight'], p[q + 'W2.bias']))
             x = g * F.relu(x1) + (1. - g) * x
             h += 1
+        return x
+
+    def _cbhg(self, x, prefix, K):
+        """CBHG (:57-139): `_cbhg_front` -> bidirectional GRU."""
+        p = self.p
+        x = self._cbhg_front(x, prefix, K)
         q = prefix + '.rnn.'
         flat = [p[q + n_] for n_ in ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0', 'weight_ih_l0_reverse',
                                      'weight_hh_l0_reverse', 'bias_ih_l0_reverse', 'bias_hh_l0_reverse')]
@@ -120,6 +131,140 @@ class TacotronInference:
         if rc != _lib.WRNN_OK:
             raise _lib.WrnnError(f'wrnn_bigru failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
         return out
+
+    # -- the encoder and the post-net through the C ABI (csrc/wrnn_cbhg.hip) ---------------------------------------------
+    def _cbhg_weights(self, c, prefix, K, keep):
+        """Fill one `wrnn_cbhg_weights` from the state dict; False if it has more highways than the struct holds."""
+        p = self.p
+
+        def ptr(name):
+            t = p[prefix + name].detach().to(self.device, torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        bank0 = p[prefix + 'conv1d_bank.0.conv.weight']
+        c.K, c.in_channels, c.channels = K, bank0.shape[1], bank0.shape[0]
+        c.proj1_channels, c.proj2_channels = p[prefix + 'conv_project1.conv.weight'].shape[0], p[prefix + 'conv_project2.conv.weight'].shape[0]
+        for k in range(K):
+            q = f'conv1d_bank.{k}.'
+            c.bank_conv_w[k] = ptr(q + 'conv.weight')
+            c.bank_bn_w[k], c.bank_bn_b[k] = ptr(q + 'bnorm.weight'), ptr(q + 'bnorm.bias')
+            c.bank_bn_mean[k], c.bank_bn_var[k] = ptr(q + 'bnorm.running_mean'), ptr(q + 'bnorm.running_var')
+        for i in (1, 2):
+            q = f'conv_project{i}.'
+            setattr(c, f'proj{i}_conv_w', ptr(q + 'conv.weight'))
+            for a, b in (('w', 'weight'), ('b', 'bias'), ('mean', 'running_mean'), ('var', 'running_var')):
+                setattr(c, f'proj{i}_bn_{a}', ptr(q + 'bnorm.' + b))
+        if prefix + 'pre_highway.weight' in p:
+            c.pre_highway_w = ptr('pre_highway.weight')
+        h = self._count(prefix + 'highways.%d.W1.weight')
+        if h > 4:
+            return False
+        c.num_highways = h
+        for i in range(h):
+            q = f'highways.{i}.'
+            c.highway_w1[i], c.highway_b1[i] = ptr(q + 'W1.weight'), ptr(q + 'W1.bias')
+            c.highway_w2[i], c.highway_b2[i] = ptr(q + 'W2.weight'), ptr(q + 'W2.bias')
+        for a, b in (('rnn_w_ih', 'weight_ih_l0'), ('rnn_w_hh', 'weight_hh_l0'), ('rnn_b_ih', 'bias_ih_l0'), ('rnn_b_hh', 'bias_hh_l0')):
+            setattr(c, a, ptr('rnn.' + b))
+            setattr(c, a + '_rev', ptr('rnn.' + b + '_reverse'))
+        return p[prefix + 'rnn.weight_hh_l0'].shape == (3 * c.channels, c.channels) and p[prefix + 'rnn.weight_ih_l0'].shape == (3 * c.channels, c.channels)
+
+    def _front_handle(self):
+        """The instance's `wrnn_taco_front` (created on first use), or None when `wrnn_taco_front_create` refuses the dims
+        (WRNN_ERR_ARG: the caller stays on the torch ops).  Any other failure raises."""
+        import ctypes
+        from . import _lib
+        if self._front is not None:
+            return self._front or None
+        if self.device.type != 'cuda':
+            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
+        L = _lib.lib()
+        p, keep = self.p, []
+        w = _lib.TacoFrontWeights()
+        w.struct_bytes = ctypes.sizeof(_lib.TacoFrontWeights)
+        w.n_symbols, w.embed_dims = p['encoder.embedding.weight'].shape
+        w.prenet1, w.prenet2 = p['encoder.pre_net.fc1.weight'].shape[0], p['encoder.pre_net.fc2.weight'].shape[0]
+        w.encoder_proj_dims, w.n_mels, w.fft_bins = p['encoder_proj.weight'].shape[0], self.n_mels, p['post_proj.weight'].shape[0]
+        for a, b in (('embedding', 'encoder.embedding.weight'), ('prenet_fc1_w', 'encoder.pre_net.fc1.weight'), ('prenet_fc1_b', 'encoder.pre_net.fc1.bias'),
+                     ('prenet_fc2_w', 'encoder.pre_net.fc2.weight'), ('prenet_fc2_b', 'encoder.pre_net.fc2.bias'), ('encoder_proj_w', 'encoder_proj.weight'),
+                     ('post_proj_w', 'post_proj.weight')):
+            t = p[b].detach().to(self.device, torch.float32).contiguous()
+            keep.append(t)
+            setattr(w, a, t.data_ptr())
+        ok = self._cbhg_weights(w.encoder_cbhg, 'encoder.cbhg.', self._enc_k, keep) if 1 <= self._enc_k <= 16 else False
+        ok = ok and (self._cbhg_weights(w.postnet, 'postnet.', self._post_k, keep) if 1 <= self._post_k <= 16 else False)
+        ok = ok and p['encoder_proj.weight'].shape[1] == 2 * w.encoder_cbhg.channels and p['post_proj.weight'].shape[1] == 2 * w.postnet.channels
+        if not ok:
+            self._front = False
+            return None
+        torch.cuda.synchronize(self.device)                                        # the tensors above may be fresh copies: create reads them
+        h = ctypes.c_void_p()
+        self._front_device = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        rc = L.wrnn_taco_front_create(ctypes.byref(w), self._front_device, ctypes.byref(h))
+        if rc == _lib.ERR_ARG:
+            self._front = False
+            self._front_refused = L.wrnn_taco_last_error().decode()
+            return None
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_front_create failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        self._front = h
+        self._front_destroy = L.wrnn_taco_front_destroy
+        return h
+
+    def __del__(self):
+        try:
+            h = getattr(self, '_front', None)
+            if h:
+                self._front = None
+                self._front_destroy(h)
+        except Exception:
+            pass
+
+    def _front_workspace(self, rows):
+        from . import _lib
+        need = int(_lib.lib().wrnn_taco_front_workspace_bytes(self._front, rows))
+        if self._front_ws is None or self._front_ws.numel() < need:
+            self._front_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._front_ws
+
+    def encode_kernel(self, ids, want_pre_rnn=False):
+        """`encode` through `wrnn_taco_encode`: (encoder_seq (1, n, 2C), its projection (1, n, D), the highway output (n, C) in front of the
+        GRU or None).  Asynchronous on the current stream."""
+        from . import _lib
+        L, h = _lib.lib(), self._front_handle()
+        if h is None:
+            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
+        dev = self.device
+        ids_d = torch.as_tensor(ids, dtype=torch.int32, device='cpu').to(dev).contiguous()
+        n = ids_d.numel()
+        seq = torch.empty(1, n, self.p['encoder_proj.weight'].shape[1], device=dev)
+        seq_proj = torch.empty(1, n, self.p['encoder_proj.weight'].shape[0], device=dev)
+        pre = torch.empty(n, seq.size(2) // 2, device=dev) if want_pre_rnn else None
+        ws = self._front_workspace(n)
+        rc = L.wrnn_taco_encode(h, ids_d.data_ptr(), n, seq.data_ptr(), seq_proj.data_ptr(), pre.data_ptr() if want_pre_rnn else None,
+                                ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_encode failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        return seq, seq_proj, pre
+
+    def postnet_kernel(self, mel, want_pre_rnn=False):
+        """The post-net CBHG and `post_proj` through `wrnn_taco_postnet`: mel (1, n_mels, N) or (n_mels, N) on the device -> (linear (N, fft),
+        the highway output (N, C) or None).  Asynchronous on the current stream."""
+        from . import _lib
+        L, h = _lib.lib(), self._front_handle()
+        if h is None:
+            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
+        dev = self.device
+        m = mel.reshape(self.n_mels, -1).to(dev, torch.float32).contiguous()
+        N = m.size(1)
+        linear = torch.empty(N, self.p['post_proj.weight'].shape[0], device=dev)
+        pre = torch.empty(N, self.p['post_proj.weight'].shape[1] // 2, device=dev) if want_pre_rnn else None
+        ws = self._front_workspace(N)
+        rc = L.wrnn_taco_postnet(h, m.data_ptr(), N, linear.data_ptr(), pre.data_ptr() if want_pre_rnn else None, ws.data_ptr(), ws.numel(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_postnet failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        return linear, pre
 
     def encode(self, ids):
         """Encoder (:24-39) + `encoder_proj` (:403-404): ids (n,) -> encoder_seq (1, n, 2C), its projection (1, n, D)."""
@@ -214,16 +359,25 @@ class TacotronInference:
         return mel, scores[:k]
 
     @torch.no_grad()
-    def generate(self, ids, steps=2000, kernel=False, kernel_variant=0):
+    def generate(self, ids, steps=2000, kernel=False, kernel_variant=0, cbhg_kernel=False):
         """`Tacotron.generate(x, steps)` (:370-430).  Returns numpy (mel (n_mels, N), linear (fft, N), attention (N, n_chars)).
 
         kernel=True (HIP device): the decoder loop runs as ONE persistent kernel (`wrnn_taco_decode`, csrc/wrnn_taco.hip; the stop
         test of :411 is evaluated inside it) and the CBHGs' bidirectional GRUs as `wrnn_bigru`.  kernel=False: the eager loop (any
         device; the CPU form is the mirror tests/test_tacotron_mirror.py pins bit-exactly to the reference).  (Round 2's HIP-graph
-        replay of one decoder step -- 555 us per step against the kernel's 27.6 -- is gone; its numbers are in profiles/r03*.)"""
+        replay of one decoder step -- 555 us per step against the kernel's 27.6 -- is gone; its numbers are in profiles/r03*.)
+
+        cbhg_kernel=True (HIP device; off by default): the encoder and the post-net run through `wrnn_taco_encode` / `wrnn_taco_postnet`
+        (csrc/wrnn_cbhg.hip) instead of the torch ops; a state dict whose dims `wrnn_taco_front_create` refuses stays on the torch ops.
+        `self.last_front_path` says which: 'hip' or 'torch'."""
         dev = self.device
+        if cbhg_kernel and dev.type != 'cuda':
+            from . import _lib
+            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
         self._bigru_kernel = bool(kernel) and dev.type == 'cuda'                   # the CBHGs' GRUs as persistent kernels too
-        seq, seq_proj = self.encode(ids)
+        front = bool(cbhg_kernel) and self._front_handle() is not None
+        self.last_front_path = 'hip' if front else 'torch'
+        seq, seq_proj = self.encode_kernel(ids)[:2] if front else self.encode(ids)
         n = seq.size(1)
         z = lambda *s: torch.zeros(*s, device=dev)
         st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
@@ -242,8 +396,11 @@ class TacotronInference:
                 if (m_ < self.stop_threshold).all() and t > 10:
                     break
         mel = torch.cat(frames, dim=2)
-        post = self._cbhg(mel, 'postnet', self._post_k)
-        linear = F.linear(post, self.p['post_proj.weight']).transpose(1, 2)[0]
+        if front:
+            linear = self.postnet_kernel(mel)[0].transpose(0, 1)
+        else:
+            post = self._cbhg(mel, 'postnet', self._post_k)
+            linear = F.linear(post, self.p['post_proj.weight']).transpose(1, 2)[0]
         attn = scores_all if kernel else torch.cat([s.unsqueeze(-1).transpose(1, 2) for s in scores_all], 1)[0]
         return mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()
 
