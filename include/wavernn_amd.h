@@ -152,7 +152,8 @@ typedef struct wrnn_options {
                                   the exchange ring with the sentinel before EVERY launch, bit 3 = no second request for x_{t-1}, bit 4 = a fresh y2 request
                                   at the top of the sampling stage, bit 5 = sampling stage at wave priority 0, bit 7 = the residual input word requested beside
                                   the operand loads (round 5), bit 20 = the hh workgroups' gh block as ONE unbroken MFMA stream (bits 21-25: yield length /
-                                  spacing of the broken one), bit 6 = placement read-out through phase_clocks (test hook), bit 8 = every layer written
+                                  spacing of the broken one), bit 6 = placement read-out through phase_clocks (test hook), bit 12 = the polling stages check all 32 operand words of a lane for the
+                                  sentinel instead of one word per 16-byte fragment (round 7; not in the phase-clock builds), bit 8 = every layer written
                                   through (no XCD-local plain stores), bit 14 = with phase_clocks: the stage time line of three steps as well
                                   (phase_clocks then holds [256 * 32 + 512 * 512] words; scripts/gpu_duo_trace.py);
                                 wrnn_sparse_kernel, wrnn_chain_kernel: bits 2, 8 as wrnn_duo_kernel; wrnn_sparse_kernel: bit 11 = the DENSE fc stages on a pack whose

@@ -63,6 +63,12 @@
 //     state): a launch leaves the sentinel in the entries of its T1 and T1 + 1, and the next launch's ih workgroups poll those as usual.
 //   * the gh words {r, z, n, tag = consuming step + 1} carry a tag instead of relying on a sentinel: no re-arm, and two ring entries
 //     suffice (the hh workgroup cannot start gh(t+3) before the ih workgroup has consumed gh(t+1): it needs h(t+2), which needs gh(t+2)).
+//     This relies on a 16-byte store being seen whole or not at all by a 16-byte load of the same address.
+//   * the operand check of a polled fragment layer relies on the same thing (round 7): every 16-byte fragment -- four consecutive k of one
+//     segment -- of h, y, the residual sums, cI and the RAW logits is written by exactly ONE lane's 16-byte store, by its publisher (publish4l, the
+//     conditioning tile's store), by the re-arm and by the host's fill alike, so ONE word of a fragment is the sentinel exactly when all four are:
+//     a lane looks at 8 of its 32 operand words (frag_there, wrnn_ring.h; wrnn_options.tuning bit 12 = all 32, for A/B).  x_t (layer 7) is written
+//     word by word and is polled word by word.
 // A launch ends with every entry in the state the next step expects (kernel end drains everything): continuations need no refill.
 #include <type_traits>
 
@@ -260,6 +266,8 @@ __device__ __forceinline__ void duo_ih(const LoopArgs &a, float *smem, const int
     // pending back half (22.5 vs 22.8 us at 4 slots).  Also measured, no effect: a static wave priority for the ih workgroups (s_setprio 1 .. 3), the
     // back halves at priority 3; the hh workgroups at a higher priority cost 4.5 %.
     const bool late_xo = (a.tuning & 128) == 0, reprobe = (a.tuning & 8) == 0;
+    const bool full_chk = !PROF && (a.tuning & 4096) != 0;      // A/B (tuning bit 12): the operand check over all 32 words of a lane instead of one per fragment (wrnn_ring.h, frag_there;
+                                                                // the profiling builds have no register to spare for the switch: they run the default)
     bool dead = false;
     int pp = 0;
     int t = T0;
@@ -443,10 +451,10 @@ __device__ __forceinline__ void duo_ih(const LoopArgs &a, float *smem, const int
         // ---------------- operands ----------------
         {
             const bool live = fi < nb;
-            const bool there = frag_there(x, live);
+            const bool there = frag_there(x, live, full_chk);
             if (PROF && tid == 0) { PROFL[cur + 6] += 1; PROFL[cur + 7] += !there; }
             if (__builtin_expect(!there, 0))
-                wait_for([&] { return frag_there(x, live); },
+                wait_for([&] { return frag_there(x, live, full_chk); },
                          [&] {
 #pragma unroll
                              for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, soff_x, 16 /* sc1 */);
@@ -644,6 +652,7 @@ __device__ __forceinline__ void duo_hh(const LoopArgs &a, float *smem, const int
     auto slot_nb = [&](int i) -> int { return (int)((nbpack >> (8 * i)) & 255u); };
 
     const bool fresh_y2 = (a.tuning & 16) != 0;
+    const bool full_chk = !PROF && (a.tuning & 4096) != 0;      // A/B (tuning bit 12): as in duo_ih
 
     const bool prio_smp = (a.tuning & 32) == 0;          // the sampling stage (on its slot's chain) runs at wave priority 3 (round 6: 16.1 vs 16.4 us per step at 2 slots, 22.56 vs 22.72 at 4; A/B: tuning bit 5 = off)
     bool dead = false;
@@ -817,10 +826,10 @@ __device__ __forceinline__ void duo_hh(const LoopArgs &a, float *smem, const int
         PHX(cur + 0);
         {
             const bool live = fi < nb;
-            const bool there = frag_there(x, live);
+            const bool there = frag_there(x, live, full_chk);
             if (PROF && tid == 0) { PROFL[cur + 6] += 1; PROFL[cur + 7] += !there; }
             if (__builtin_expect(!there, 0))
-                wait_for([&] { return frag_there(x, live); },
+                wait_for([&] { return frag_there(x, live, full_chk); },
                          [&] {
 #pragma unroll
                              for (int r = 0; r < 8; ++r) x[r] = __builtin_amdgcn_raw_buffer_load_b128(xrs, voff_frag + r * 1024, soff_x, 16 /* sc1 */);

@@ -379,6 +379,21 @@ __device__ __forceinline__ bool frag_there(const u32x4 (&x)[8], bool live)
     return __all(m != SENT || !live);
 }
 
+// The same over ONE word of every 16-byte fragment (full == false: the default of wrnn_duo.hip since round 7; full: all 32 words, for A/B).  A
+// fragment -- four consecutive k of one segment -- is written by exactly one lane's 16-byte store wherever it is written: the publish
+// (publish4l; cI: the conditioning tile's store), the re-arm (16-byte stores of the sentinel) and the host's fill; a reader's 16-byte load sees
+// such a store whole or not at all -- what the tagged {r, z, n, tag} gh words of wrnn_duo.hip rely on too -- so the fragment's last word says as
+// much as its four.  (Layers written word by word -- x_t -- are never checked this way.)
+__device__ __forceinline__ bool frag_there(const u32x4 (&x)[8], bool live, bool full)
+{
+    unsigned m = max(max(max(x[0].w, x[1].w), max(x[2].w, x[3].w)), max(max(x[4].w, x[5].w), max(x[6].w, x[7].w)));
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) m = max(max(m, x[r].x), max(x[r].y, x[r].z));
+    }
+    return __all(m != SENT || !live);
+}
+
 // A bounded wait that does not fail the launch's control flow: `there()` (wave-uniform) is re-evaluated after every `reload()`; when
 // the spin limit expires or another workgroup has raised the abort flag the wave marks itself dead -- it skips every later wait and
 // runs on with whatever the buffers hold (its barrier sequence is unchanged, nothing hangs, wrnn_status() reports the failure).
