@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 9   /* v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
+#define WRNN_ABI_VERSION 9   /* v9 + wrnn_options.sparse_groups (appended; struct_bytes tells whether a caller has it: the number stays, every v9 caller runs as it did): two groups per cluster of wrnn_sparse_kernel, on request.  v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
 
 enum {
     WRNN_OK = 0,
@@ -69,7 +69,8 @@ enum {
     WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
                                four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
                                (wrnn_pack_sparse_blocks) and >= 256 CUs; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
-                               step is the latency of one chain, sixteen chains run side by side (csrc/wrnn_sparse.hip) */
+                               step is the latency of one chain, sixteen chains run side by side (csrc/wrnn_sparse.hip).  wrnn_options.sparse_groups = 2: TWO groups
+                               per cluster, stage by stage through the same weights (MOL with block-sparse Linear layers; 512 segments a round) */
 };
 
 /*
@@ -135,7 +136,7 @@ typedef struct wrnn_run_info {
 typedef struct wrnn_options {
     int32_t struct_bytes;
     int32_t algo;            /* WRNN_ALGO_*                                                                  (default AUTO) */
-    int32_t depth;           /* groups in flight per cluster, 1..8 (sparse: always 1); 0 = the library picks */
+    int32_t depth;           /* groups in flight per cluster, 1..8 (sparse: does not apply -- see sparse_groups); 0 = the library picks */
     int32_t clusters;        /* loop kernel: clusters to use (1, 2 or 4); 0 = the library picks */
     int32_t cond_valu;       /* stream kernel: 1 = hoisted conditioning on VALU instead of MFMA (cross-check) */
     int32_t slab_steps;      /* loop kernel: conditioning slab length in steps; 0 = sized to ~96 MB */
@@ -189,6 +190,15 @@ typedef struct wrnn_options {
     int32_t mel_scale;       /* stretch factor of the last stage */
     const float *mel_taps;   /* HOST [2 * mel_scale + 1]: upsample.up_layers.5.weight */
     const int32_t *seg_moff; /* HOST [n_segments] */
+    /* wrnn_sparse_kernel, on request (`auto` never sets it): groups of <= 16 segments per 16-CU cluster.  0 or 1 = one (the default: every plan, workspace
+     * size and output is what it was); 2 = two -- a round takes 32 groups (512 segments): groups 0-15 are the first slot of clusters 0-15, groups 16-31 the
+     * second, and every stage of a step runs for the first slot and then for the second, so that one slot's exchange hops pass under the other's work.  A
+     * segment's samples do not depend on it (same arithmetic, same order).  wrnn_run_info then reports depth = 2 and rounds = ceil(groups / 32); state, ring
+     * and aux tables are sized for it by wrnn_workspace_bytes*.  Built for MOL packs whose Linear layers are block-sparse too (wrnn_pack_sparse_fc_blocks()
+     * > 0).  WRNN_ERR_ARG: any other value; 2 on a call that does not run wrnn_sparse_kernel, on 9-bit RAW, on dense Linear layers (also tuning bit 11), or
+     * with phase_clocks.  A caller whose struct_bytes ends before this field gets 0.  wrnn_abi_version() does NOT tell whether a library knows the field (it
+     * stays 9): a library built before it reads only its own shorter struct and silently runs one group -- ask wrnn_plan_segments() and look at depth. */
+    int32_t sparse_groups;
 } wrnn_options;
 
 const char *wrnn_last_error(void);

@@ -20,6 +20,7 @@ ap.add_argument('--prune-linear', action='store_true', help='... and fc1 / fc2 (
 ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'probe.json'))
 ap.add_argument('--B', default='12,24,64,128,192,256,512')
 ap.add_argument('--variants', default='auto,g1,g2,g4,g8')
+ap.add_argument('--sparse-groups', type=int, default=0, choices=[0, 1, 2], help='wrnn_options.sparse_groups of every `sparse` variant (the variant s2 always runs two groups per cluster)')
 ap.add_argument('--so', default=None, help='A/B builds: load this libwavernn_amd*.so instead of the in-tree one')
 args = ap.parse_args()
 
@@ -41,6 +42,7 @@ VARS = {'auto': dict(algo='auto'), 'stream': dict(algo='stream'), 'g1': dict(alg
         'nola': dict(algo='loop', tuning=1), 'fence': dict(algo='loop', tuning=2), 'nola-fence': dict(algo='loop', tuning=3),
         'c1': dict(algo='chain', depth=1), 'c2': dict(algo='chain', depth=2), 'c3': dict(algo='chain', depth=3), 'c4': dict(algo='chain', depth=4),
         's1': dict(algo='sparse'), 'swt': dict(algo='sparse', tuning=256),       # wrnn_sparse_kernel (needs --prune); swt: every layer written through
+        's2': dict(algo='sparse', sparse_groups=2),                              # ... two groups per cluster (needs --prune-linear too)
         # wrnn_duo_kernel (round 4): tuning bit 0 = loads first, bit 1 = publish first (default: by depth), bit 8 = every layer written through
         # (no XCD-local plain stores), bit 2 = ring re-filled before every launch
         'd1': dict(algo='duo', depth=1), 'd2': dict(algo='duo', depth=2), 'd3': dict(algo='duo', depth=3), 'd4': dict(algo='duo', depth=4),
@@ -75,6 +77,8 @@ for B in [int(x) for x in args.B.split(',')]:
         opts = dict(VARS[v.split('+')[0]])
         if '+' in v:                                                  # 'd4+0x10AA1000': the variant with this wrnn_options.tuning word
             opts['tuning'] = int(v.split('+')[1], 0)
+        if opts.get('algo') == 'sparse' and args.sparse_groups:
+            opts.setdefault('sparse_groups', args.sparse_groups)
         try:
             depth = opts.get('depth', 0)
             if depth > 1 and B <= 64 * (depth - 1) and opts['algo'] in ('loop', 'duo', 'chain', 'octo'):
@@ -87,7 +91,7 @@ for B in [int(x) for x in args.B.split(',')]:
                 ref = o
             err = float(np.abs(o - ref).max())
             info = eng.last_run_info()
-            row = dict(variant=v, B=B, T=T, ms=round(ms, 3), us_per_round_step=round(ms * 1e3 / (T * max(info['rounds'], 1)), 3),
+            row = dict(variant=v, B=B, T=T, ms=round(ms, 3), us_per_round_step=round(ms * 1e3 / (T * max(info['rounds'], 1)), 3), us_per_step=round(ms * 1e3 / T, 3),
                        seg_steps_per_s=round(B * T / (ms * 1e-3)), info=info, max_dev_vs_first=err)
         except Exception as e:
             row = dict(variant=v, B=B, error=str(e)[:200])

@@ -12,6 +12,7 @@ from wavernn_amd.synthetic import random_state_dict
 ap = argparse.ArgumentParser()
 ap.add_argument('--B', type=int, default=256); ap.add_argument('--T', type=int, default=1200); ap.add_argument('--tuning', type=int, default=0)
 ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'sparse_phase_clocks.json')); ap.add_argument('--linear', action='store_true')
+ap.add_argument('--sparse-groups', type=int, default=0, choices=[0, 1, 2], help='wrnn_options.sparse_groups; 2 (needs --linear): the plain timing only -- the phase-clock build has one group per cluster')
 a = ap.parse_args()
 dev = torch.device('cuda', 0)
 sd, _ = block_prune_state_dict(random_state_dict(0, mode='MOL'), 0.95, (16, 1), linear=a.linear)
@@ -23,8 +24,13 @@ mels_up = torch.from_numpy(rs.uniform(0, 1, (L, 80)).astype(np.float32)).to(dev)
 aux = torch.from_numpy(rs.uniform(-1, 1, (L // hop, 128)).astype(np.float32)).to(dev)
 noise = torch.empty(a.T, 11 * a.B, device=dev).uniform_(1e-5, 1 - 1e-5)
 for _ in range(2):
-    eng.run(mels_up, aux, a.B, a.T, stride, noise, hop, algo='sparse', tuning=a.tuning)
+    eng.run(mels_up, aux, a.B, a.T, stride, noise, hop, algo='sparse', tuning=a.tuning, sparse_groups=a.sparse_groups)
 plain = eng.last_loop_ms()
+if a.sparse_groups == 2:
+    res = {'plain_ms': plain, 'us_per_step': plain * 1e3 / a.T, 'B': a.B, 'T': a.T, 'tuning': a.tuning, 'sparse_groups': 2, 'info': eng.last_run_info()}
+    print(json.dumps(res))
+    json.dump(res, open(a.out, 'w'), indent=1)
+    sys.exit(0)
 pc = torch.zeros(256, 32, dtype=torch.int64, device=dev)
 eng.run(mels_up, aux, a.B, a.T, stride, noise, hop, algo='sparse', tuning=a.tuning, phase_clocks=pc)
 prof_ms = eng.last_loop_ms()

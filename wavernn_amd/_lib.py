@@ -116,7 +116,7 @@ class Options(ctypes.Structure):
                [('force_x', ctypes.c_void_p), ('logits', ctypes.c_void_p), ('phase_clocks', ctypes.c_void_p), ('timer', ctypes.c_void_p),
                 ('info', ctypes.POINTER(RunInfo)), ('progress', ctypes.c_void_p), ('progress_user', ctypes.c_void_p),
                 ('mel_stage', ctypes.c_int32), ('mel_rows', ctypes.c_int32), ('mel_scale', ctypes.c_int32),
-                ('mel_taps', ctypes.c_void_p), ('seg_moff', ctypes.c_void_p)]
+                ('mel_taps', ctypes.c_void_p), ('seg_moff', ctypes.c_void_p), ('sparse_groups', ctypes.c_int32)]
 
     def __init__(self, **kw):
         super().__init__(**kw)

@@ -330,6 +330,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
             # segment-step -- is drawn and uploaded in slices of steps, at most `model.noise_chunk_bytes` of it resident (the bound
             # WaveRNN.generate() keeps); any other kernel takes the whole call's noise at once
             steps = T
+            groups = model.loop_sparse_groups(eng, n_seg, T) if hasattr(model, 'loop_sparse_groups') else 0      # (model.sparse_groups; 0 unless wrnn_sparse_kernel is planned)
             if eng.plan(n_seg, T, algo=model.loop_algo)['kernel'] in RESUMABLE_KERNELS:
                 per_step = n_seg * (11 if mode == 'MOL' else model.n_classes) * 4
                 steps = max(1, min(T, getattr(model, 'noise_chunk_bytes', 2 << 30) // per_step))
@@ -338,7 +339,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for t0 in range(0, T, steps):
                     t1 = min(T, t0 + steps)
                     eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(t1 - t0), hop, algo=model.loop_algo, check=check, out=out_view,
-                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1))
+                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1), sparse_groups=groups)
             except ResidencyError as e:
                 # the persistent grid was refused (on the first slice: a continuation cannot change kernels).  The other loop kernels read
                 # the up-sampled mel in full; the engine then degrades as usual on an unsliced call (one workgroup per CU, then the
@@ -350,7 +351,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for u in gens:
                     gens[u].manual_seed(int(seeds[u]))
                     burn_ctor_draws(model.rnn_dims, model.aux_dims, 'cpu', gens[u])
-                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view)
+                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view, sparse_groups=groups)
             finally:
                 if pool is not None:
                     pool.shutdown()

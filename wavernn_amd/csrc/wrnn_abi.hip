@@ -29,8 +29,9 @@ size_t duo_xbuf_bytes(int G);
 size_t duo_xbuf_bytes_max();
 hipError_t launch_sparse(const LoopArgs &args, int nbp, int mode, hipStream_t stream);
 int sparse_clusters(int n_cus);
-size_t sparse_state_floats();
-size_t sparse_xbuf_bytes();
+int sparse_max_slots();
+size_t sparse_state_floats(int slots);
+size_t sparse_xbuf_bytes(int slots);
 hipError_t launch_put_floats(float *dst, const float *src, int n, hipStream_t stream);
 hipError_t launch_chain(const LoopArgs &args, int mode, hipStream_t stream);
 hipError_t launch_octo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
@@ -463,9 +464,9 @@ const KindDesc KINDS[N_KINDS] = {
     /* K_CHAIN   */ {"wrnn_chain_kernel", 16, 4, true, true, true, chain_clusters, [](int) { return chain_max_depth(); }, chain_state_floats,
                      chain_xbuf_bytes, chain_xbuf_bytes,
                      [](const LoopArgs &a, int, int, int mode, hipStream_t s) { return launch_chain(a, mode, s); }},
-    // (16 clusters of 16 CUs, one group each)
-    /* K_SPARSE  */ {"wrnn_sparse_kernel", 64, 3, true, true, true, sparse_clusters, [](int) { return 1; }, [](int) { return sparse_state_floats(); },
-                     [](int) { return sparse_xbuf_bytes(); }, [](int) { return sparse_xbuf_bytes(); },
+    // (16 clusters of 16 CUs, one group each: max_depth is what wrnn_options.depth and `auto` can reach; wrnn_options.sparse_groups = 2 plans two, make_plan)
+    /* K_SPARSE  */ {"wrnn_sparse_kernel", 64, 3, true, true, true, sparse_clusters, [](int) { return 1; }, sparse_state_floats,
+                     sparse_xbuf_bytes, sparse_xbuf_bytes,
                      [](const LoopArgs &a, int, int nbp, int mode, hipStream_t s) { return launch_sparse(a, nbp, mode, s); }},
 };
 
@@ -556,6 +557,11 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
         set_err("unknown algo %d", algo);
         return WRNN_ERR_ARG;
     }
+    if (o->sparse_groups < 0 || o->sparse_groups > sparse_max_slots()) {
+        set_err("wrnn_options.sparse_groups = %d: 0 or 1 (one group per cluster) or 2", o->sparse_groups);
+        return WRNN_ERR_ARG;
+    }
+    const bool two_groups = o->sparse_groups == 2;
     const int groups = (B + SEG - 1) / SEG;
     pl->kind = K_STREAM; pl->ncl = 0; pl->G = 0; pl->rounds = 1; pl->per_round = B; pl->slab = T; pl->ngr_max = groups;
     if (p->generic) {           // non-shipped hparams: the dimension-generic kernel is the only one that takes them
@@ -564,6 +570,7 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
             return WRNN_ERR_ARG;
         }
         if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
+        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_generic_kernel)"); return WRNN_ERR_ARG; }
         pl->kind = K_GENERIC;
         return WRNN_OK;
     }
@@ -617,8 +624,24 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     }
     const KindDesc &k = KINDS[kind];
     pl->kind = kind;
+    // two groups per cluster of wrnn_sparse_kernel: on request only, and only what is instantiated -- MOL with gathered fc stages (the dense fc tiles leave
+    // no register room: <64, false> spills as it is), no phase clocks
+    if (two_groups) {
+        if (kind != K_SPARSE) {
+            set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on %s)", k.name);
+            return WRNN_ERR_ARG;
+        }
+        if (p->mode != WRNN_MODE_MOL) { set_err("wrnn_options.sparse_groups = 2: wrnn_sparse_kernel's 9-bit RAW form is built with one group per cluster only"); return WRNN_ERR_ARG; }
+        if (!p->sp_fc || (o->tuning & 2048)) {
+            set_err("wrnn_options.sparse_groups = 2: needs a pack whose Linear layers are block-sparse too (wrnn_pack_sparse_fc_blocks() > 0) and their gathered fc "
+                    "stages: the dense fc tiles leave no registers for a second group");
+            return WRNN_ERR_ARG;
+        }
+        if (o->phase_clocks && !(o->tuning & 64)) { set_err("wrnn_options.sparse_groups = 2: the phase-clock build of wrnn_sparse_kernel has one group per cluster only"); return WRNN_ERR_ARG; }
+    }
     if (k.persistent) {
-        plan_split(pl, B, ncl, k.max_depth(p->mode), o->depth);
+        if (two_groups) plan_split(pl, B, ncl, sparse_max_slots(), sparse_max_slots());      // depth 2, rounds = ceil(groups / 32)
+        else plan_split(pl, B, ncl, k.max_depth(p->mode), o->depth);
         pl->slab = o->slab_steps >= 1 ? o->slab_steps : default_slab(*pl, p->mode);      // (an explicit slab length is taken as given -- short slabs included: tests)
         if (pl->slab > T) pl->slab = T;
         pl->tab_fps = DUO_TAB_FPS;

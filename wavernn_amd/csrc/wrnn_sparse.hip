@@ -36,6 +36,13 @@
 //   * the conditioning is the duo kernel's: cI and (wrnn_options.mel_stage) the last up-sampling stage formed inside the loop, per-segment
 //     aux tables per slab of <= 1,651 steps, a launch per slab, 16 floats of state per (unit, segment) between launches: the workspace
 //     depends on neither T nor the corpus.
+//   * TWO groups per cluster on request (wrnn_options.sparse_groups = 2; NS = 2, MOL with gathered fc stages): groups 16 .. 31 of a round are a SECOND slot of
+//     clusters 0 .. 15.  The weights (AGPRs, LDS) are shared; a slot owns its region of the exchange buffer (group g: region g, its tagged x words included), its
+//     segment table in LDS, its gh accumulators / cell state / W_ih . cI accumulators / residual words, and its 16 floats of saved state per (unit, segment).
+//     Every stage of a step runs for slot 0 and then for slot 1 -- straight-line code as before, one slot's hop passes under the other slot's stage --, with ONE
+//     drain and ONE barrier at the top of the step.  Per slot every wave keeps the one-group kernel's order of polls, publications and re-arms, so its skew
+//     arguments hold per slot; across slots nothing is inferred.  A slot without a group is skipped by every wave.  A segment's arithmetic is the one-group
+//     kernel's: its samples do not depend on cluster or slot.  Model: tests/test_sparse_two_groups_exchange_model.py; device: tests/test_gpu_sparse_two_groups.py.
 // Skipping exact zeros changes no partial sum; the summation ORDER differs from the dense kernels (surviving columns ascending, four
 // at a time), so parity is to the MoL tolerance (tests/test_gpu_parity.py, tests/test_gpu_fullsize.py).
 // 9-bit RAW (MODE 0, every difference behind `if constexpr`: the MOL instantiations are the code they were): fc2 publishes y2, fc3 (512 x 512) is a dense
@@ -58,9 +65,9 @@ static_assert(SPCLUSTERS <= LMAXG * MAXCL, "one exchange-buffer region per clust
 static_assert(SPCLUSTERS * SPWG <= XCC_WORDS, "placement table");
 
 struct SpLds {
-    int off_seg, off_part, off_log, off_misc, off_prof, off_ct1, off_f3, off_lgt, total;
+    int off_seg, off_part, off_log, off_misc, off_prof, off_ct1, off_f3, off_lgt, off_seg1, total;
 };
-__host__ __device__ inline SpLds sp_lds(bool raw = false)
+__host__ __device__ inline SpLds sp_lds(bool raw = false, int slots = 1)
 {
     SpLds l;
     int o = 0;
@@ -73,6 +80,7 @@ __host__ __device__ inline SpLds sp_lds(bool raw = false)
     l.off_ct1 = o;  o += 5 * 64 * (CK + 4);   // rnn2's cI-forming workgroups: the I-layer tiles [wave 0..3 | wave 0's SECOND block][kk | bias][lane]
     l.off_f3 = o;   o += 2 * XT;             // the sampling workgroup: fc3 (30 x 512 = two 16-row tiles) in A-fragment order; RAW: every workgroup's 32 rows of fc3
     l.off_lgt = o;  if (raw) o += SEG * LDC;  // RAW, the sampling workgroups: the gathered logits [segment][class], stride LDC
+    l.off_seg1 = o; if (slots > 1) o += 64;   // two groups per cluster: the segment table of the SECOND slot (behind everything: the one-group carve is what it was)
     l.total = o;
     return l;
 }
@@ -155,6 +163,27 @@ __device__ __forceinline__ void fc_tile_init(FcTile<MPW> &ft, const float *vals,
     }
 }
 
+// What ONE group of segments owns inside a workgroup (NS = 2: a cluster runs two groups, "slots", through the same weights -- item 5 of the header):
+// its region of the exchange buffer, its segments, its 16 floats of saved state per (unit, segment), and the registers a step hands to the next.
+struct SpSlot {
+    int cbase, nb, b0g;                                 // byte offset of the region; segments of the group (0: no such group in this round); its first segment in the call
+    bool live;                                          // this lane's segment exists (gate stages, fragment polls)
+    float *state_wg;
+    int *SEGT;                                          // LDS: 16 positions | 16 limits | 16 table-row bases of this slab | 16 mel offsets
+    float h[4];                                         // the GRU state of the lane's four units (fatchord_version.py:194-195: zeros)
+    float ghr[4], ghz[4], ghn[4];                       // gh(t) = W_hh . h(t - 1) + b_hh of those units: formed during step t - 1, kept here
+    f32x4 gacc[3];                                      // rnn1: W_ih1 . cI(t), formed at the end of step t - 1
+    u32x4 own;                                          // the lane's own words of the gates' input layer (cI / x1) = the residual input
+};
+// a stage lambda works on the slot it is handed: the names the one-group code has always used, bound to that slot
+#define SP_SLOT(S)                                                                                              \
+    const int cbase = (S).cbase, nb = (S).nb, b0g = (S).b0g;                                                    \
+    const bool live = (S).live;                                                                                 \
+    float *const state_wg = (S).state_wg;                                                                       \
+    int *const SEGT = (S).SEGT;                                                                                 \
+    auto &h = (S).h; auto &ghr = (S).ghr; auto &ghz = (S).ghz; auto &ghn = (S).ghn; auto &gacc = (S).gacc; auto &own = (S).own; \
+    (void)cbase; (void)nb; (void)b0g; (void)live; (void)state_wg; (void)SEGT; (void)h; (void)ghr; (void)ghz; (void)ghn; (void)gacc; (void)own
+
 __device__ __forceinline__ unsigned max4(const u32x4 &q) { return max(max(q.x, q.y), max(q.z, q.w)); }
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define SPX(k)                                                                 \
@@ -197,14 +226,14 @@ __device__ __forceinline__ void mfma2(const float (&a0)[AF], const float (&a1)[A
 // tiles, 10 cI(t+2) formed; 15 = steps.  RAW (MODE 0), every workgroup: 11 wait y2, 12 fc3 -> logits; the sampling workgroups: 13 wait logits, 14 sampling
 // (9-bit RAW: fc3 is a dense 512 x 512 stage of every workgroup -- 32 rows each, K split over the 4 waves, A in LDS -- published as layer 16, and FOUR
 // rnn2 workgroups sample, one segment per wave: see the kernel's comment)
-template <int NBP, bool FCS, int MODE, bool LA, bool PROF>
+template <int NBP, bool FCS, int MODE, bool LA, bool PROF, int NS>
 __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const int rg, const int gid, const int ub, const int wgi, const bool loc)
 {
     constexpr int MPW = NBP / 4;
     constexpr bool MOL = MODE == 1;
-    const SpLds L = sp_lds(!MOL);
+    static_assert(NS == 1 || (NS == 2 && MOL && FCS && !PROF), "two groups per cluster: MOL with gathered fc stages");
+    const SpLds L = sp_lds(!MOL, NS);
     float *PART = smem + L.off_part, *fc3b = smem + L.off_log, *F3 = smem + L.off_f3, *LGT = smem + L.off_lgt;
-    int *SEGT = reinterpret_cast<int *>(smem + L.off_seg);
     u64 *PROFL = reinterpret_cast<u64 *>(smem + L.off_prof);
     u64 plast = 0;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -225,10 +254,21 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     const float *const mels_up = a.mels_up, *const aux_fr = a.aux_fr, *const mel_coef = a.mel_coef;
     const int mel_stage = a.mel_stage;
     const int NR = a.Btot, NGR = a.NG;
-    const int b0 = (int)(((long)gid * NR) / NGR), nb = (int)(((long)(gid + 1) * NR) / NGR) - b0;
-    const int b0g = a.rb0 + b0;                         // first segment of the group in the call
     constexpr int L_H = LA ? 0 : 1, L_XR = LA ? 5 : 6, L_IN = LA ? 4 : 5;
-    float *const state_wg = a.state + (size_t)gid * SPSTATE_CL + (size_t)wgi * SPSTATE_WG;
+    // slot s of this cluster runs group gid + 16 s of the round, in region rg + 16 s of the exchange buffer (a group has ITS region and ITS saved state
+    // wherever it runs); a slot without a group (nb = 0) is never stepped, polled or waited for
+    SpSlot sl[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int g = gid + SPCLUSTERS * s;
+        const bool there = NS == 1 || g < NGR;
+        const int b0 = there ? (int)(((long)g * NR) / NGR) : 0;
+        sl[s].nb = there ? (int)(((long)(g + 1) * NR) / NGR) - b0 : 0;
+        sl[s].b0g = a.rb0 + b0;                         // first segment of the group in the call
+        sl[s].cbase = (rg + SPCLUSTERS * s) * DSLOTB;
+        sl[s].state_wg = a.state + (size_t)g * SPSTATE_CL + (size_t)wgi * SPSTATE_WG;
+        sl[s].SEGT = reinterpret_cast<int *>(smem + (s == 0 ? L.off_seg : L.off_seg1));
+    }
     // MOL: rnn2's workgroup 0 samples.  RAW: rnn2's workgroups 0, 5, 6, 7 -- sampler sidx = 0 .. 3, wave w: segment 4 sidx + w -- the rnn2 workgroups with
     // the least to do behind fc3 (0 forms no cI; 5-7 one block per wave, 1-4 a second one on wave 0): a sampler's gh stage and cI block follow its sampling
     const bool sampler = !LA && (ub == 0 || (!MOL && ub >= 5));
@@ -314,34 +354,39 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             for (int i = 0; i < 4; ++i) CT1[(CK + i) * 64 + lane] = c1.bias[i];
         }
     }
-    if (tid < SEG) {
-        const int sc = b0g + (tid < nb ? tid : nb - 1);
-        const int pos = a.seg_pos[sc];
-        SEGT[tid] = pos;
-        SEGT[SEG + tid] = a.seg_lim[sc];
-        SEGT[2 * SEG + tid] = sc * a.tab_fps - (pos + a.tab_t0) / a.hop;
-        SEGT[3 * SEG + tid] = a.mel_stage ? a.seg_moff[sc] : 0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        SP_SLOT(sl[s]);
+        if (tid < SEG && (NS == 1 || nb > 0)) {
+            const int sc = b0g + (tid < nb ? tid : nb - 1);
+            const int pos = a.seg_pos[sc];
+            SEGT[tid] = pos;
+            SEGT[SEG + tid] = a.seg_lim[sc];
+            SEGT[2 * SEG + tid] = sc * a.tab_fps - (pos + a.tab_t0) / a.hop;
+            SEGT[3 * SEG + tid] = a.mel_stage ? a.seg_moff[sc] : 0;
+        }
     }
     __syncthreads();
 
     const __amdgpu_buffer_rsrc_t xrs = make_rsrc(a.xbuf, (unsigned)(DXBUF_FLOATS * 4));
     const __amdgpu_buffer_rsrc_t crs = make_rsrc(a.c2f, 0x7FFFF000u);          // rnn2: per-frame table of its aux columns + b_ih2
     const __amdgpu_buffer_rsrc_t f1rs = make_rsrc(a.c3f, 0x7FFFF000u), f2rs = make_rsrc(a.c4f, 0x7FFFF000u);
-    const int cbase = rg * DSLOTB;
     const int voff_frag = frag_off(w, 0, lane) * 4;      // fc stages: this lane's first fragment of a layer (bytes)
     const int voff_blk = rb * 1024 + lane * 16;          // gate stages: this lane's quarter-row of the wave's 1 KB block of a k-major layer (re-arm stores)
     const int voff_own = u0 * 64 + fi * 4;               // ... the word of (unit u0, segment fi) in a k-major layer; units u0 + e: + 64 e
-    const bool live = fi < nb;                           // this lane's segment exists (gate stages, fragment polls)
 
     bool dead = false;
     int pp = 0;
     int t = T0;
-    float h[4] = {0.f, 0.f, 0.f, 0.f};                   // the GRU state of the lane's four units (fatchord_version.py:194-195: zeros)
-    float ghr[4], ghz[4], ghn[4];                        // gh(t) = W_hh . h(t - 1) + b_hh of those units: formed during step t - 1, kept here
-    f32x4 gacc[3];                                       // rnn1: W_ih1 . cI(t), formed at the end of step t - 1
-    u32x4 own = {0u, 0u, 0u, 0u};                        // the lane's own words of the gates' input layer (cI / x1) = the residual input
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+    sl[s].live = fi < sl[s].nb;
+    SP_SLOT(sl[s]);
+    own = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = 0.f;
     gacc[0] = gacc[1] = gacc[2] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (resume) {
+    if (resume && (NS == 1 || nb > 0)) {
         const float4 hv = *reinterpret_cast<const float4 *>(state_wg + tid * 16), r4 = *reinterpret_cast<const float4 *>(state_wg + tid * 16 + 4),
                      z4 = *reinterpret_cast<const float4 *>(state_wg + tid * 16 + 8), n4 = *reinterpret_cast<const float4 *>(state_wg + tid * 16 + 12);
         h[0] = hv.x; h[1] = hv.y; h[2] = hv.z; h[3] = hv.w;
@@ -350,6 +395,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { ghr[e] = bh[0][e]; ghz[e] = bh[1][e]; ghn[e] = bh[2][e]; }      // W_hh . 0 + b_hh
+    }
     }
 
     // the lane's four units of a k-major layer (h1 h2 x1 cI: the layers the gate stages GATHER from -- [k][16 segments], 64 contiguous bytes
@@ -373,7 +419,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     };
     // ring hygiene (header): after the last poll of step t this wave resets its OWN words of entry (t + 2) % 4 in the sentinel layers it
     // publishes: its quarters of the workgroup's two y1 and two y2 blocks (one 16-lane group each), its block of h and of the residual sum
-    auto rearm = [&]() {
+    auto rearm = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int so = cbase + ((t + DAHEAD_IH) & (DRING - 1)) * XTB;
         const u32x4 q = {SENT, SENT, SENT, SENT};
         if constexpr (FCS) {
@@ -386,7 +433,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     };
 
     // ---------------- fc stage: relu(fc1([x2, a3])) -> y1 (which = 1) / relu(fc2([y1, a4])) -> y2 (which = 2), the workgroup's 32 rows
-    auto fc = [&](auto WC) {
+    auto fc = [&](SpSlot &S, auto WC) {
+        SP_SLOT(S);
         constexpr int which = decltype(WC)::value;
         constexpr int LI = which == 1 ? 6 : 2, LO = which == 1 ? 2 : 3;
         const int sb = cbase + (t & (DRING - 1)) * XTB;
@@ -449,7 +497,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
                         store16(pl[1], 16 * DLAYERB + (2 * wgi + (w & 1)) * 1024 + lane * 16, sb);
                     } else store16(q, LO * DLAYERB + (2 * wgi + (w & 1)) * 1024 + lane * 16, sb);      // y2: read by the dense fc3 of the sampling workgroup -> fragment order
                 }
-                rearm();                                // (behind this wave's last sentinel poll of the step; tests/test_sparse_exchange_model.py, SparseFcSim)
+                rearm(S);                               // (behind this wave's last sentinel poll of the step; tests/test_sparse_exchange_model.py, SparseFcSim)
             }
             SPX(LA ? (which == 1 ? 5 : 7) : (which == 1 ? 3 : 7));
         } else {
@@ -479,7 +527,7 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         lds_barrier();
         publish4l(xrs, sb + LO * DLAYERB + (2 * wgi) * 1024, tid, fmaxf(get_partial<2>(PW, 0, pu, pj) + cv0, 0.f), pj < nb, loc);
         publish4l(xrs, sb + LO * DLAYERB + (2 * wgi + 1) * 1024, tid, fmaxf(get_partial<2>(PW, 1, pu, pj) + cv1, 0.f), pj < nb, loc);
-        if constexpr (which == 2) rearm();              // (behind the last poll of the step -- y1(t) above -- and behind the publication: off the chain)
+        if constexpr (which == 2) rearm(S);             // (behind the last poll of the step -- y1(t) above -- and behind the publication: off the chain)
         pp ^= 1;
         SPX(LA ? (which == 1 ? 5 : 7) : (which == 1 ? 3 : 7));
         }
@@ -488,7 +536,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     // ---------------- gate stages ----------------
     // the GRU cell of the lane's four units (ATen gru_cell; hardware exp / rcp as the duo kernel's MoL path) and the publication of
     // the residual sum (on the chain: first) and of h
-    auto cell_publish = [&](const float (&gir)[4], const float (&giz)[4], const float (&gin)[4], const float (&xin)[4]) {
+    auto cell_publish = [&](SpSlot &S, const float (&gir)[4], const float (&giz)[4], const float (&gin)[4], const float (&xin)[4]) {
+        SP_SLOT(S);
         u32x4 qx, qh;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -508,12 +557,14 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     // rnn1, front half: W_ih1 . cI(ts) of the wave's rows + the lane's own cI words (the residual input xi - w0 x), as soon as cI(ts) is there.
     // In two parts, so that the forming of cI(ts + 1) runs under the gather's latency: issue | ... | finish
     unsigned fv[3][MPW];
-    auto front_issue = [&](int ts) {
+    auto front_issue = [&](SpSlot &S, int ts) {
+        SP_SLOT(S);
         const int so = cbase + L_IN * DLAYERB + (ts & (DRING - 1)) * XTB;
         gather_issue(xrs, so, gi, fv);
         own = load_own(so);
     };
-    auto front_finish = [&](int ts) {
+    auto front_finish = [&](SpSlot &S, int ts) {
+        SP_SLOT(S);
         const int so = cbase + L_IN * DLAYERB + (ts & (DRING - 1)) * XTB;
         if (__builtin_expect(!gather_there(fv, max4(own), live), 0))
             wait_for([&] { return gather_there(fv, max4(own), live); }, [&] { gather_issue(xrs, so, gi, fv); own = load_own(so); }, status, dead, 0x720u, ts);
@@ -522,7 +573,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         SPX(9);
     };
     // rnn1, back half (the chain: sampling -> here): x_{t-1} arrives as a tagged word {x, tag = t}
-    auto back_a = [&]() {
+    auto back_a = [&](SpSlot &S) {
+        SP_SLOT(S);
         float xv = 0.f;
         if (t > T0) {
             const int sx = cbase + 7 * DLAYERB + ((t - 1) & 1) * XTB;
@@ -541,11 +593,12 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             gin[e] = gacc[2][e] + fmaf(xv, ux[2][e], cb[2][e]);
             xin[e] = fmaf(w0o[e], xv, __uint_as_float(own[e]));      // xi of the lane's units (:208-209)
         }
-        cell_publish(gir, giz, gin, xin);
+        cell_publish(S, gir, giz, gin, xin);
         SPX(1);
     };
     // rnn2: the whole gate stage is on the chain (x1 -> here)
-    auto gates_b = [&]() {
+    auto gates_b = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int so = cbase + L_IN * DLAYERB + (t & (DRING - 1)) * XTB;
         unsigned v[3][MPW];
         gather_issue(xrs, so, gi, v);
@@ -576,11 +629,12 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             gin[e] = o2[e] + __uint_as_float(c2[2][e]);
             xin[e] = __uint_as_float(own[e]);
         }
-        cell_publish(gir, giz, gin, xin);
+        cell_publish(S, gir, giz, gin, xin);
         SPX(1);
     };
     // gh(t + 1) = W_hh . h(t) + b_hh of the wave's rows (h(t) of the whole layer gathered from the ring): stays in this lane's registers
-    auto gh_stage = [&]() {
+    auto gh_stage = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int so = cbase + L_H * DLAYERB + (t & (DRING - 1)) * XTB;
         unsigned v[3][MPW];
         gather_issue(xrs, so, gh, v);
@@ -604,7 +658,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), xrs, vo + 64 * e, soff, 16 /* sc1 */);
         }
     };
-    auto cond_step = [&](int tt) {
+    auto cond_step = [&](SpSlot &S, int tt) {
+        SP_SLOT(S);
         const int p = SEGT[fi] + tt;
         const bool valid = live && p < SEGT[SEG + fi];
         const int fr = magic ? (int)(__umulhi((unsigned)p, magic) >> mshift) : p / hop;
@@ -631,7 +686,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         SPX(10);
     };
     // rnn2's workgroup 0: fc3 (30 x 512: two 16-row tiles in A-fragment order, in LDS) + the mixture-of-logistics sampling of step t
-    auto sample = [&]() {
+    auto sample = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int sb = cbase + (t & (DRING - 1)) * XTB;
         // x[r] = this wave's fragments of y2 -- or (fold3) the tile-0 partial logits of the fc2 row blocks 8 w + r (rows 4 kq + e of segment fi: the
         // accumulators' layout, the same addresses); x1[r]: their tile-1 partial logits (layer 16)
@@ -699,7 +755,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     // y2 rows 128 w .. 128 w + 127), 2 x 32 MFMAs per wave with A from LDS, partial tiles through LDS, one barrier, the bias -> layer 16 (fragment order),
     // then the wave's re-arm of its quarter of the workgroup's two layer-16 blocks in entry (t + 2) % 4: behind its workgroup's poll of y2(t) of every
     // workgroup (the barrier), which needed every sampler past its sampling of step t - 1 (tests/test_sparse_raw_exchange_model.py)
-    auto fc3_raw = [&]() {
+    auto fc3_raw = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int sb = cbase + (t & (DRING - 1)) * XTB;
         u32x4 x[8];
 #pragma unroll
@@ -726,7 +783,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     };
     // RAW, sampling workgroup sidx: the logits of the group's 16 segments gathered into LDS (wave w: rows 128 w .. 128 w + 127), then wave w samples segment
     // 4 sidx + w (wrnn_raw.h) and publishes x_t as a tagged word; noise row t - noise_t0 of the call's [T][segment][512] noise
-    auto sample_raw = [&]() {
+    auto sample_raw = [&](SpSlot &S) {
+        SP_SLOT(S);
         const int sb = cbase + 16 * DLAYERB + (t & (DRING - 1)) * XTB;
         const int sj = 4 * sidx + w, sjc = sj < nb ? sj : nb - 1;
         float qn[8];
@@ -773,13 +831,24 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     if (PROF && tid == 0) plast = __builtin_amdgcn_s_memtime();
+    // every stage runs for slot 0 and then, where the cluster has a second group in this round, for slot 1 (NS = 1: the one-group kernel's stream).  A
+    // slot's events keep the order and the waits they have in the one-group kernel -- the other slot's stages are time that passes --, so every
+    // "has seen X => Y is done" of the header holds per slot; nothing can wait in a circle, because a wave waits in stage k of slot s of step t only
+    // for publications of (step, stage, slot) triples that come earlier in that order (tests/test_sparse_two_groups_exchange_model.py)
+    auto each = [&](auto &&stage) __attribute__((always_inline)) {
+        stage(sl[0]);
+        if constexpr (NS > 1) {
+            if (sl[1].nb > 0) stage(sl[1]);
+        }
+    };
     if constexpr (LA) {
-        front_issue(T0);
-        front_finish(T0);
+        each([&](SpSlot &S) { front_issue(S, T0); front_finish(S, T0); });
     } else if (cond_wg) {                               // the two (FCS: three) steps a launch starts with; every later cI is formed CLEAD steps ahead
-        cond_step(T0);
-        if (T0 + 1 < T1) cond_step(T0 + 1);
-        if (FCS && T0 + 2 < T1) cond_step(T0 + 2);
+        each([&](SpSlot &S) {
+            cond_step(S, T0);
+            if (T0 + 1 < T1) cond_step(S, T0 + 1);
+            if (FCS && T0 + 2 < T1) cond_step(S, T0 + 2);
+        });
     }
     // FCS: cI THREE steps ahead -- its readers (end of step t + 2) have seen x_{t+1}, i.e. every wave of the cluster has passed the top of step t + 1 =
     // the forming wave's drain; two ahead leaned on "y1(t + 1) needed every x2(t + 1)", which a gathered fc stage does not give (SparseFcSim)
@@ -792,29 +861,29 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
         if constexpr (LA) {
             // Off the chain, placed where this workgroup waits anyway (profiles/r05b .. r05d_sparse_phase_clocks.json): gh(t + 1) while x1 -> rnn2
             // -> x2 is under way, W_ih . cI(t + 1) under the sampling of step t.
-            back_a();
-            gh_stage();                                 // (needs h1(t) of every rnn1 workgroup: one hop behind the publication above)
-            fc(I1{});
-            fc(I2{});
-            if constexpr (!MOL) fc3_raw();
-            if (t + 1 < T1) { front_issue(t + 1); front_finish(t + 1); }
+            each(back_a);
+            each(gh_stage);                             // (needs h1(t) of every rnn1 workgroup: one hop behind the publication above)
+            each([&](SpSlot &S) { fc(S, I1{}); });
+            each([&](SpSlot &S) { fc(S, I2{}); });
+            if constexpr (!MOL) each(fc3_raw);
+            if (t + 1 < T1) each([&](SpSlot &S) { front_issue(S, t + 1); front_finish(S, t + 1); });
         } else {
             // gh(t + 1) is needed at the cell of step t + 1: behind fc2 (and, in the sampling workgroup, behind the sampling) it sits in the
             // wait for x1(t + 1); between fc1 and fc2 its gather outlasted y1's hop and held up y2 (r05b phase clocks).  The non-sampling
             // workgroups then form cI(t + 2): it overwrites cI(t - 2), gathered by every rnn1 workgroup at the end of its step t - 3; it is
             // drained at the top of step t + 1, before x2(t + 1) goes out, and gathered by workgroups that have polled y1(t + 1), which needed
             // x2(t + 1) of every rnn2 workgroup (header).
-            gates_b();
-            fc(I1{});
-            fc(I2{});
+            each(gates_b);
+            each([&](SpSlot &S) { fc(S, I1{}); });
+            each([&](SpSlot &S) { fc(S, I2{}); });
             if constexpr (MOL) {
-                if (sampler) sample();
+                if (sampler) each(sample);              // (one ping-pong pair of partial-tile sets serves both slots: a set is rewritten two samplings later, behind a barrier)
             } else {
-                fc3_raw();
-                if (sampler) sample_raw();
+                each(fc3_raw);
+                if (sampler) each(sample_raw);
             }
-            gh_stage();
-            if (cond_wg && t + CLEAD < T1) cond_step(t + CLEAD);
+            each(gh_stage);
+            if (cond_wg && t + CLEAD < T1) each([&](SpSlot &S) { cond_step(S, t + CLEAD); });
         }
     }
     if (PROF && tid == 0 && a.prof) {
@@ -822,6 +891,8 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
     }
     // ---- what the next launch of this round needs: h and gh(T1) of every (unit, segment), rnn1: x_{T1-1}; the workgroups that form cI leave the sentinel in the cI
     //      entries of steps T1 and T1 + 1 (the next launch polls its first two steps)
+    each([&](SpSlot &S) {
+    SP_SLOT(S);
     *reinterpret_cast<float4 *>(state_wg + tid * 16) = make_float4(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<float4 *>(state_wg + tid * 16 + 4) = make_float4(ghr[0], ghr[1], ghr[2], ghr[3]);
     *reinterpret_cast<float4 *>(state_wg + tid * 16 + 8) = make_float4(ghz[0], ghz[1], ghz[2], ghz[3]);
@@ -841,13 +912,16 @@ __device__ __forceinline__ void sp_role(const LoopArgs &a, float *smem, const in
             if (cond2) store16(q, cblk1 * 1024 + lane * 16, cbase + 4 * DLAYERB + ((T1 + e) & (DRING - 1)) * XTB);
         }
     }
+    });
 }
 
 // Grid = 16 clusters x 16 workgroups of 256 threads (one per CU), cooperative launch.  Placement (speed only, verified at run time): block
 // b is observed to run on XCD b % 8 and the blocks of an XCD to be dealt round-robin over its 32 CUs.  XCD x hosts clusters x (its CUs
 // 0-15) and 8 + x (CUs 16-31); CU c of a cluster: c / 8 = rnn1 | rnn2, unit block c % 8.  Group g of a round runs on cluster g: the first
 // eight groups take one cluster on every XCD.
-template <int NBP, bool FCS, int MODE, bool PROF>
+// NS = 2 (wrnn_options.sparse_groups = 2): groups 16 .. 31 of the round are the SECOND slot of clusters 0 .. 15 -- a cluster has a second slot only when
+// it has a first, and with <= 16 groups no cluster has one.
+template <int NBP, bool FCS, int MODE, bool PROF, int NS = 1>
 __global__ __launch_bounds__(NT, 1) void wrnn_sparse_kernel(const LoopArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -887,15 +961,18 @@ __global__ __launch_bounds__(NT, 1) void wrnn_sparse_kernel(const LoopArgs a)
         if (a.tuning & 256) loc = false;                // A/B: everything written through
         __syncthreads();
     }
-    if (cu < 8) sp_role<NBP, FCS, MODE, true, PROF>(a, smem, cl, cl, cu, cu, loc);
-    else sp_role<NBP, FCS, MODE, false, PROF>(a, smem, cl, cl, cu - 8, cu, loc);
+    if (cu < 8) sp_role<NBP, FCS, MODE, true, PROF, NS>(a, smem, cl, cl, cu, cu, loc);
+    else sp_role<NBP, FCS, MODE, false, PROF, NS>(a, smem, cl, cl, cu - 8, cu, loc);
 }
 
 // clusters of 16 CUs: the kernel's block -> role map is written for the whole 256-CU chip
 int sparse_clusters(int n_cus) { return n_cus >= SPCLUSTERS * SPWG ? SPCLUSTERS : 0; }
-size_t sparse_state_floats() { return (size_t)SPCLUSTERS * SPSTATE_CL; }
-size_t sparse_xbuf_bytes() { return (size_t)SPCLUSTERS * DSLOTB; }      // the regions a launch touches: a prefix of the duo kernel's buffer
-size_t sparse_lds_bytes(int mode) { return (size_t)sp_lds(mode == 0).total * sizeof(float); }
+constexpr int SPSLOTS = 2;                   // groups per cluster on request (wrnn_options.sparse_groups)
+static_assert(SPSLOTS * SPCLUSTERS <= LMAXG * MAXCL, "one exchange-buffer region per group of a round");
+int sparse_max_slots() { return SPSLOTS; }
+size_t sparse_state_floats(int slots) { return (size_t)slots * SPCLUSTERS * SPSTATE_CL; }
+size_t sparse_xbuf_bytes(int slots) { return (size_t)slots * SPCLUSTERS * DSLOTB; }      // the regions a launch touches: a prefix of the duo kernel's buffer
+size_t sparse_lds_bytes(int mode, int slots) { return (size_t)sp_lds(mode == 0, slots).total * sizeof(float); }
 
 template <int MODE>
 const void *sparse_fn(int nbp, bool fcs, bool prof)
@@ -909,12 +986,15 @@ const void *sparse_fn(int nbp, bool fcs, bool prof)
 // mode: 1 = MOL, 0 = 9-bit RAW (512 classes: fc3 from fc3_w, the noise of the call in `noise`)
 hipError_t launch_sparse(const LoopArgs &args, int nbp, int mode, hipStream_t stream)
 {
-    if ((nbp != 48 && nbp != 64) || !args.u1 || !args.xcc_tab || !args.sp_vals || args.NG < 1 || args.NG > SPCLUSTERS) return hipErrorInvalidValue;
+    const int slots = args.G == SPSLOTS ? SPSLOTS : 1;               // groups per cluster (the planner: 2 only for what is instantiated below)
+    if ((nbp != 48 && nbp != 64) || !args.u1 || !args.xcc_tab || !args.sp_vals || args.NG < 1 || args.NG > slots * SPCLUSTERS) return hipErrorInvalidValue;
     if (mode == 1 ? !args.fc3f : (mode != 0 || args.C != H || !args.noise)) return hipErrorInvalidValue;
-    const size_t lds = sparse_lds_bytes(mode);
+    const size_t lds = sparse_lds_bytes(mode, slots);
     const bool prof = args.prof && !(args.tuning & 64);              // phase clocks (wrnn_options.phase_clocks)
     const bool fcs = args.sp_fc_vals != nullptr;                     // the pack's Linear layers are block-sparse too: gathered fc stages
-    const void *fn = mode == 1 ? sparse_fn<1>(nbp, fcs, prof) : sparse_fn<0>(nbp, fcs, prof);
+    if (slots > 1 && (mode != 1 || !fcs || prof)) return hipErrorInvalidValue;      // two groups: MOL with gathered fc stages, no phase clocks
+    const void *fn = slots > 1 ? (nbp == 48 ? (const void *)wrnn_sparse_kernel<48, true, 1, false, SPSLOTS> : (const void *)wrnn_sparse_kernel<64, true, 1, false, SPSLOTS>)
+                   : mode == 1 ? sparse_fn<1>(nbp, fcs, prof) : sparse_fn<0>(nbp, fcs, prof);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     LoopArgs a = args;

@@ -136,13 +136,14 @@ class LoopEngine:
         seg_lim = np.full(B, L, dtype=np.int32)
         return self.run_segments(mels_up, aux, seg_pos, seg_lim, T, noise, hop, **kw)
 
-    def options(self, algo='auto', depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, tuning=0):
+    def options(self, algo='auto', depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, tuning=0, sparse_groups=0):
         if algo == 'auto' and self._auto_floor is not None:      # (after a refused cooperative launch: see run_segments)
             algo = self._auto_floor
         o = _lib.Options()
         o.algo = _lib.ALGOS[algo]
         o.depth, o.clusters, o.slab_steps, o.cond_valu = int(depth), int(clusters), int(slab_steps), int(bool(cond_valu))
         o.tuning = int(tuning)
+        o.sparse_groups = int(sparse_groups or 0)      # wrnn_sparse_kernel: 2 = two groups per cluster (on request; any other kernel refuses it)
         if t_range is not None:
             o.t_begin, o.t_end = int(t_range[0]), int(t_range[1])
         return o
@@ -160,13 +161,14 @@ class LoopEngine:
 
     def run_segments(self, mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo='auto', force_x=None, want_logits=False,
                      check=True, depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, out=None, logits=None,
-                     phase_clocks=None, tuning=0, progress=None, _fallback=False):
+                     phase_clocks=None, tuning=0, progress=None, sparse_groups=0, _fallback=False):
         """mels_up (L,feat) / aux (n_frames,4*aux_dims) / noise: float32 CUDA tensors; seg_pos / seg_lim: host
         int32 arrays (B,) -- segment b, step t reads position seg_pos[b]+t, zero conditioning from seg_lim[b] on
         (several utterances: concatenated conditioning).  Returns out (B,T) CUDA [and logits (T,B,C)].
         Enqueues on the current stream; `check=True` synchronises and raises if a kernel gave up.
 
-        depth / clusters / slab_steps / cond_valu: `wrnn_options` (0 = the library picks).  t_range=(t0, t1) runs only those
+        depth / clusters / slab_steps / cond_valu / sparse_groups: `wrnn_options` (0 = the library picks; sparse_groups=2: two groups per
+        cluster of wrnn_sparse_kernel, same samples).  t_range=(t0, t1) runs only those
         steps; t0 > 0 continues the previous call on this engine's workspace (pass the same `out`; `noise` then holds the
         rows of [t0, t1) only) -- how long RAW runs draw their noise in chunks instead of T*B*C floats at once.
         progress: optional `f(steps_done, T, n_segments)` called from a HIP runtime thread when the device has finished each
@@ -194,7 +196,7 @@ class LoopEngine:
         if noise.numel() != need:
             raise ValueError(f'noise has {noise.numel()} elements, expected {need}')
         n_frames = int(aux.shape[0])
-        o = self.options(algo, depth, clusters, slab_steps, cond_valu, t_range, tuning)
+        o = self.options(algo, depth, clusters, slab_steps, cond_valu, t_range, tuning, sparse_groups)
         nbytes = int(self.lib.wrnn_workspace_bytes_segments(self._pack, B, T, n_frames, ctypes.byref(o)))
         if nbytes == 0:
             raise _lib.WrnnError('bad geometry / options: ' + self.lib.wrnn_last_error().decode())
@@ -233,7 +235,7 @@ class LoopEngine:
             # the persistent grid is not co-resident right now (CU masking, a smaller partition, another cooperative kernel).  `auto`
             # degrades step by step (FALLBACK_ALGO): wrnn_sparse_kernel -> two workgroups per CU (wrnn_duo_kernel) -> one (wrnn_loop_kernel;
             # each has its own workspace layout, continuations are pinned to the kernel the first slice ran on) -> the stream kernel (any
-            # device, no inter-workgroup traffic; whole calls only)
+            # device, no inter-workgroup traffic; whole calls only).  sparse_groups is a speed hint for wrnn_sparse_kernel: the next kernel runs without it
             import warnings
             why = self.lib.wrnn_last_error().decode()
             planned = _lib.RunInfo()
@@ -250,7 +252,7 @@ class LoopEngine:
                     self._progress_keep.pop()       # (the retry registers its own thunk)
                 res = self.run_segments(mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo=nxt, depth=depth, clusters=clusters, force_x=force_x,
                                         want_logits=want_logits, check=check, slab_steps=slab_steps, cond_valu=cond_valu, t_range=t_range, out=out,
-                                        logits=logits, phase_clocks=phase_clocks, tuning=tuning, progress=progress, _fallback=True)
+                                        logits=logits, phase_clocks=phase_clocks, tuning=tuning, progress=progress, _fallback=True)      # (sparse_groups: wrnn_sparse_kernel's alone -- dropped)
                 if algo == 'auto':
                     self._auto_floor = self._auto_floor or nxt       # later `auto` calls start from the kernel that ran (no refused launch + workspace re-allocation per call)
                 return res
@@ -270,7 +272,7 @@ class LoopEngine:
         self._launches = (self._launches if t0 > 0 else 0) + int(self._info.launches)
         if t0 == 0:
             self._slice_algo = KERNEL_ALGOS.get((self._info.kernel or b'').decode(), (None, None))[0]
-        self._last_opts = (B, T, n_frames, self.options(algo, depth, clusters, slab_steps, cond_valu, None))
+        self._last_opts = (B, T, n_frames, self.options(algo, depth, clusters, slab_steps, cond_valu, None, 0, sparse_groups))
         if check:
             rc = self.lib.wrnn_status(self._ws.data_ptr(), stream)      # synchronises the stream: every queued progress call has run
             del self._progress_keep[:]

@@ -49,6 +49,8 @@ def main(argv=None):
     ap.add_argument('--overlap', '-o', type=int, default=550)
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--seed', type=int, default=None, help='parity noise: utterance u uses torch.manual_seed(seed + u)')
+    ap.add_argument('--sparse-groups', type=int, default=None, choices=[1, 2],
+                    help='a pruned MoL model on wrnn_sparse_kernel: groups of segments per cluster (2: 512 segments a round; a dense model ignores it)')
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
@@ -66,6 +68,7 @@ def main(argv=None):
     model = WaveRNN(**SHIPPED, mode=a.mode).to(dev)
     if a.weights:
         model.load(a.weights)
+    model.sparse_groups = a.sparse_groups
     paths, mels = load_mels(a.mels)
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
     outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group,

@@ -131,6 +131,10 @@ class WaveRNN(nn.Module):
         self.noise_source = 'cpu'
         #: 'auto' | 'loop' | 'sparse' | 'stream'  (WRNN_ALGO_*, include/wavernn_amd.h)
         self.loop_algo = 'auto'
+        #: 2 = a run planned on wrnn_sparse_kernel puts TWO groups of <= 16 segments on each of its 16 clusters (wrnn_options.sparse_groups: 512 segments a
+        #: round instead of 256, the same samples; MoL models whose Linear layers are pruned too).  None (default) = one group.  A run on any other
+        #: kernel -- a dense model, or the next kernel after a refused cooperative launch -- ignores it.
+        self.sparse_groups = None
         #: 'native' = the HIP pre-loop kernels (MFMA MelResNet + box-filter up-sampling, wrnn_pre_*);
         #: 'torch' = the nn.Modules below through PyTorch-ROCm (MIOpen)
         self.pre_algo = 'native'
@@ -240,6 +244,13 @@ class WaveRNN(nn.Module):
         except _lib.WrnnError:
             return False
 
+    def loop_sparse_groups(self, eng, n_segments, T):
+        """`wrnn_options.sparse_groups` of a run over this many segments: `self.sparse_groups` where the run is planned on wrnn_sparse_kernel, else 0."""
+        groups = int(self.sparse_groups or 0)
+        if groups <= 1 or eng.plan(n_segments, T, algo=self.loop_algo)['kernel'] != 'wrnn_sparse_kernel':
+            return 0
+        return groups
+
     def conditioning(self, mels, rows=False):
         """Pre-loop stage (reference :183-186) without the Stretch2d repeat of aux and without the fold:
         returns mels_up (L, feat), aux frames (N, res_out), wave_len.  rows=True (see `mel_rows_ok`): an `engine.MelRows` -- the input of
@@ -304,9 +315,10 @@ class WaveRNN(nn.Module):
             chunk = -(-T // (-(-T // chunk)))                # equal slices (no short tail slice with its own launches)
             rng_state = torch.get_rng_state() if (self.noise_source == 'cpu' and (chunk < T or rows)) else None
             algo = self.loop_algo
+            groups = self.loop_sparse_groups(eng, B, T)
             import warnings
             try:
-                out = self._run_sliced(eng, mels_up, aux, B, T, stride, chunk, algo, device)
+                out = self._run_sliced(eng, mels_up, aux, B, T, stride, chunk, algo, device, groups)
             except _lib.ResidencyError as e:
                 # `auto` picked a persistent kernel but its cooperative launch was refused (CU masking, a smaller partition, another
                 # cooperative kernel).  From the same point of the noise stream: with the mel one stage short (only wrnn_duo_kernel reads
@@ -318,7 +330,7 @@ class WaveRNN(nn.Module):
                     warnings.warn(f'wavernn_amd: {e}; up-sampling the mel in full for the other loop kernels')
                     mels_up, aux, _ = self.conditioning(mels)
                     try:
-                        out = self._run_sliced(eng, mels_up, aux, B, T, stride, chunk, algo, device)
+                        out = self._run_sliced(eng, mels_up, aux, B, T, stride, chunk, algo, device, groups)
                         e = None
                     except _lib.ResidencyError as e2:
                         e = e2
@@ -347,7 +359,7 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def _run_sliced(self, eng, mels_up, aux, B, T, stride, chunk, algo, device):
+    def _run_sliced(self, eng, mels_up, aux, B, T, stride, chunk, algo, device, sparse_groups=0):
         """The loop in slices of `chunk` steps: each slice draws its own rows of sampling noise and continues the loop where the
         previous one stopped (wrnn_options.t_begin / t_end), so at most `noise_chunk_bytes` of noise are resident.
         `progress_callback(steps_done, T, B, seconds)`, if set, is driven by wrnn_options.progress: a host function enqueued
@@ -362,7 +374,7 @@ class WaveRNN(nn.Module):
             t1 = min(T, t0 + chunk)
             noise = draw_steps(self.mode, B, t1 - t0, self.n_classes, device, self.noise_source)
             out = eng.run(mels_up, aux, B, T, stride, noise, self.hop_length, algo=algo, out=out,
-                          t_range=None if (t0 == 0 and t1 == T) else (t0, t1), progress=prog)
+                          t_range=None if (t0 == 0 and t1 == T) else (t0, t1), progress=prog, sparse_groups=sparse_groups)
         return out
 
     def gen_display(self, i, seq_len, b_size, gen_rate):
