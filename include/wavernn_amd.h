@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 9   /* v9 + wrnn_options.sparse_groups (appended; struct_bytes tells whether a caller has it: the number stays, every v9 caller runs as it did): two groups per cluster of wrnn_sparse_kernel, on request.  v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
+#define WRNN_ABI_VERSION 9   /* v9 + wrnn_options.noise_lib / noise_seed / noise_seg_id, wrnn_noise_fill, wrnn_noise_fill_host (appended like sparse_groups: the number stays): the sampling noise drawn inside the library.  v9 + wrnn_options.sparse_groups (appended; struct_bytes tells whether a caller has it: the number stays, every v9 caller runs as it did): two groups per cluster of wrnn_sparse_kernel, on request.  v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
 
 enum {
     WRNN_OK = 0,
@@ -199,6 +199,19 @@ typedef struct wrnn_options {
      * with phase_clocks.  A caller whose struct_bytes ends before this field gets 0.  wrnn_abi_version() does NOT tell whether a library knows the field (it
      * stays 9): a library built before it reads only its own shorter struct and silently runs one group -- ask wrnn_plan_segments() and look at depth. */
     int32_t sparse_groups;
+    /* The sampling noise drawn INSIDE the library from a counter-based generator (Philox4x32-10, csrc/wrnn_philox.h) instead of read from `noise`.
+     * 0 (default): every plan, workspace size and output is what it was.  1: the `noise` argument of wrnn_generate* must be NULL (a pointer is
+     * WRNN_ERR_ARG: no caller may believe their tensor was used); for every conditioning slab the library fills that slab's noise into the workspace, on the
+     * stream, in front of the slab's loop launches -- the values wrnn_noise_fill() writes for the same (seed, ids, steps), so the samples are those of the
+     * same call fed that tensor.  The value of (segment b, step t, index j) depends on noise_seed, the segment's id, t and j alone: not on the batch the
+     * segment runs in, its position in it, the slab length, the step range of a continued call or the kernel.  The workspace grows by one slab of noise:
+     * MOL 11 * n_segments floats per step, RAW n_classes * n_segments (the one-launch kernels wrnn_stream_kernel / wrnn_generic_kernel: all T steps; RAW on a
+     * kernel that forms its conditioning in the loop: the default slab is what holds 2 GB of noise, at most 4096 steps, instead of 4096).  WRNN_ERR_ARG: any
+     * other value.  A caller whose struct_bytes ends before these fields gets 0; as with sparse_groups, wrnn_abi_version() does not tell whether a library knows
+     * them -- the symbol wrnn_noise_fill does. */
+    int32_t noise_lib;
+    uint64_t noise_seed;           /* the Philox key of the call */
+    const uint64_t *noise_seg_id;  /* HOST [n_segments]: the 64-bit stream id of every segment; NULL: segment b has id b */
 } wrnn_options;
 
 const char *wrnn_last_error(void);
@@ -230,7 +243,7 @@ size_t wrnn_workspace_bytes(const wrnn_pack *p, const wrnn_geometry *g, const wr
  *
  *   mels_up  device [L, M]          un-folded up-sampled mel  (`mels` of :186 before the fold)
  *   aux      device [n_frames, 4A]  MelResNet output per FRAME (`aux` of :186 before Stretch2d repeats it)
- *   noise    device, the sampling noise in the order the reference draws it:
+ *   noise    device, the sampling noise in the order the reference draws it; NULL exactly when wrnn_options.noise_lib = 1:
  *              MOL: [T, 11*B]: per step 10*B uniforms (segment-major, mixture-minor; distribution.py:106)
  *                   followed by B uniforms (distribution.py:118), all U(1e-5, 1-1e-5)
  *              RAW: [T, B, C] Exp(1) variates (Categorical.sample -> multinomial)
@@ -260,6 +273,20 @@ int wrnn_generate_segments(const wrnn_pack *p, int32_t n_segments, int32_t T, co
                            void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream);
 size_t wrnn_workspace_bytes_segments(const wrnn_pack *p, int32_t n_segments, int32_t T, int32_t n_frames,
                                      const wrnn_options *opt);
+
+/*
+ * The sampling noise of wrnn_options.noise_lib = 1 as a tensor: steps [t_begin, t_end) of n_segments segments in the layout `noise` has above
+ * (MOL: [t_end - t_begin, 11 * n_segments], n_classes ignored; RAW: [t_end - t_begin, n_segments, n_classes]); row 0 is step t_begin.
+ * Philox4x32-10 with key = seed and counter = (t, j / 4, id of the segment): word j % 4 of that block makes the value of index j -- MOL: j = 0..9 the
+ * mixture-selection uniforms, j = 10 the logistic one, each a float32 in [1e-5, 1 - 1e-5]; RAW: j = class, an Exp(1) variate, finite and > 0
+ * (the two formulas: csrc/wrnn_philox.h).  seg_id: HOST [n_segments] or NULL (segment b has id b).
+ * wrnn_noise_fill: `out` is a DEVICE pointer (16-byte aligned); asynchronous on `stream`.  wrnn_noise_fill_host: `out` is a HOST pointer; computed by the
+ * calling thread, the HIP runtime is not touched.  The MOL values of the two are bit-identical; the RAW values differ by the two logf implementations.
+ */
+int wrnn_noise_fill(int mode, int32_t n_segments, int32_t n_classes, int32_t t_begin, int32_t t_end, uint64_t seed, const uint64_t *seg_id,
+                    float *out, int device, void *stream);
+int wrnn_noise_fill_host(int mode, int32_t n_segments, int32_t n_classes, int32_t t_begin, int32_t t_end, uint64_t seed, const uint64_t *seg_id,
+                         float *out);
 
 /* What wrnn_generate_segments WOULD run for this many segments under these options (kernel, split, rounds, slab length),
  * without launching anything.  `launches` is left 0. */

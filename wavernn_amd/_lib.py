@@ -23,7 +23,7 @@ ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': 
 #: every symbol include/wavernn_amd.h declares
 EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_create', 'wrnn_pack_destroy',
            'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
-           'wrnn_generate_segments', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
+           'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
@@ -116,7 +116,8 @@ class Options(ctypes.Structure):
                [('force_x', ctypes.c_void_p), ('logits', ctypes.c_void_p), ('phase_clocks', ctypes.c_void_p), ('timer', ctypes.c_void_p),
                 ('info', ctypes.POINTER(RunInfo)), ('progress', ctypes.c_void_p), ('progress_user', ctypes.c_void_p),
                 ('mel_stage', ctypes.c_int32), ('mel_rows', ctypes.c_int32), ('mel_scale', ctypes.c_int32),
-                ('mel_taps', ctypes.c_void_p), ('seg_moff', ctypes.c_void_p), ('sparse_groups', ctypes.c_int32)]
+                ('mel_taps', ctypes.c_void_p), ('seg_moff', ctypes.c_void_p), ('sparse_groups', ctypes.c_int32),
+                ('noise_lib', ctypes.c_int32), ('noise_seed', ctypes.c_uint64), ('noise_seg_id', ctypes.c_void_p)]
 
     def __init__(self, **kw):
         super().__init__(**kw)
@@ -186,6 +187,9 @@ def lib():
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.POINTER(Options), ctypes.c_void_p]
+    L.wrnn_noise_fill.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    L.wrnn_noise_fill_host.argtypes = L.wrnn_noise_fill.argtypes[:8]
     L.wrnn_plan_segments.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Options), ctypes.POINTER(RunInfo)]
     L.wrnn_timer_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_timer_destroy.argtypes = [ctypes.c_void_p]
@@ -236,3 +240,17 @@ def lib():
 def check(rc, what):
     if rc != WRNN_OK:
         raise WrnnError(f'{what} failed (rc={rc}): {lib().wrnn_last_error().decode()}')
+
+
+def noise_fill_host(mode, n_segments, n_classes, t_begin, t_end, seed, seg_id=None):
+    """`wrnn_noise_fill_host`: the noise the library draws for steps [t_begin, t_end) (wrnn_options.noise_lib) as a host float32 array in the layout of
+    `noise` -- MOL (t_end - t_begin, 11 * n_segments), RAW (t_end - t_begin, n_segments, n_classes).  No HIP device is needed."""
+    import numpy as np
+    mol = mode == 'MOL'
+    out = np.empty((t_end - t_begin, 11 * n_segments) if mol else (t_end - t_begin, n_segments, n_classes), np.float32)
+    ids = None if seg_id is None else np.ascontiguousarray(seg_id, dtype=np.uint64)
+    if ids is not None and ids.shape != (n_segments,):
+        raise ValueError('seg_id: one 64-bit id per segment')
+    check(lib().wrnn_noise_fill_host(MODE_MOL if mol else MODE_RAW, n_segments, n_classes, t_begin, t_end, int(seed) & (2 ** 64 - 1),
+                                     None if ids is None else ids.ctypes.data, out.ctypes.data), 'wrnn_noise_fill_host')
+    return out

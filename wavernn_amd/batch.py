@@ -174,6 +174,14 @@ def pack_noise(mode: str, plan: Plan, per_utt, lo: int = 0, hi: Optional[int] = 
     return out.contiguous() if is_torch else np.ascontiguousarray(out)
 
 
+def library_seg_ids(seed, folds, first_fold: int = 0) -> np.ndarray:
+    """The 64-bit noise stream ids (wrnn_options.noise_seg_id) of `folds` consecutive folded segments of ONE utterance, from its fold `first_fold` on:
+    (seed & 0xffffffff) << 32 | fold index.  What `WaveRNN.generate()` (seed = model.noise_seed) and `generate_corpus(noise_source='library')`
+    (seed = seeds[u]) both use -- the reason an utterance's audio does not depend on the batch, chunk or shard it was generated in."""
+    hi = np.uint64((int(seed) & 0xffffffff) << 32)
+    return hi | np.arange(first_fold, first_fold + int(folds), dtype=np.uint64)
+
+
 def chunk_utterances(plan: Plan, lo: int, hi: int, max_segments: int):
     """Cut the utterances that own segments in [lo, hi) into consecutive chunks whose segment count in [lo, hi) stays
     <= max_segments (a single longer utterance makes its own chunk).  Returns [(utterances, seg_lo, seg_hi)]."""
@@ -205,7 +213,10 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
     (on every rank), equal to per-utterance `generate(mel_u, ..., batched=True, target, overlap, mu_law)` calls.
 
     noise_source='device' draws the block's noise from the device generator instead (what the reference does when it
-    runs on a GPU; not comparable with a CPU run; `seeds` unused).  finish='all': every rank unfolds every utterance;
+    runs on a GPU; not comparable with a CPU run; `seeds` unused).  noise_source='library': the loop draws its noise itself
+    (wrnn_options.noise_lib; key `model.noise_key`), segment `i` of utterance u under the stream id `library_seg_ids(seeds[u], ...)`: one engine
+    call per chunk, no noise tensor, and every utterance equal to `generate()` alone with `model.noise_source = 'library'` and
+    `model.noise_seed = seeds[u]`, whatever the chunking and the rank count.  finish='all': every rank unfolds every utterance;
     'own': a rank unfolds only the utterances whose first segment lies in its block (None elsewhere in the list).
 
     The rank's block is processed in chunks of whole utterances of at most `max_segments_per_launch` segments, so the
@@ -224,9 +235,11 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
     """
     import torch.distributed as dist
     from .rng import draw_steps
-    if noise_source == 'cpu' and seeds is None:
-        raise ValueError("noise_source='cpu' (parity noise) needs `seeds` (one per utterance); "
+    if noise_source in ('cpu', 'library') and seeds is None:
+        raise ValueError(f"noise_source={noise_source!r} needs `seeds` (one per utterance); "
                          "pass noise_source='device' to draw from the device generator instead")
+    if noise_source not in ('cpu', 'device', 'library'):
+        raise ValueError(f'unknown noise source {noise_source!r}')
     world = dist.get_world_size(group) if group is not None else 1
     rank = dist.get_rank(group) if group is not None else 0
     if shard is not None:
@@ -306,8 +319,20 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                     gens[u] = torch.Generator(device='cpu').manual_seed(int(seeds[u]))
                     burn_ctor_draws(model.rnn_dims, model.aux_dims, 'cpu', gens[u])
 
+            lib_ids = None
+            if noise_source == 'library':
+                lib_ids = np.concatenate([library_seg_ids(seeds[u], min(chi, int(plan.first[u] + plan.folds[u])) - max(clo, int(plan.first[u])),
+                                                          max(clo, int(plan.first[u])) - int(plan.first[u])) for u in utts])
+                assert lib_ids.shape == (n_seg,)
+            lib_kw = dict(noise_seed=int(getattr(model, 'noise_key', 0)), noise_seg_id=lib_ids) if lib_ids is not None else {}
+
             def draw(steps_):
                 """noise rows of the next `steps_` loop steps of this chunk's segments, on the device"""
+                if noise_source == 'library':
+                    if loop_fn is None:
+                        return None              # (the loop draws it)
+                    from ._lib import noise_fill_host
+                    return torch.from_numpy(noise_fill_host(mode, n_seg, model.n_classes, 0, steps_, lib_kw['noise_seed'], lib_ids)).to(device)
                 if noise_source != 'cpu':
                     return draw_steps(mode, n_seg, steps_, model.n_classes, device, 'device')
                 def one(u):        # (ATen releases the GIL inside the fill: the utterances' independent streams are drawn side by side)
@@ -331,7 +356,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
             # WaveRNN.generate() keeps); any other kernel takes the whole call's noise at once
             steps = T
             groups = model.loop_sparse_groups(eng, n_seg, T) if hasattr(model, 'loop_sparse_groups') else 0      # (model.sparse_groups; 0 unless wrnn_sparse_kernel is planned)
-            if eng.plan(n_seg, T, algo=model.loop_algo)['kernel'] in RESUMABLE_KERNELS:
+            if noise_source != 'library' and eng.plan(n_seg, T, algo=model.loop_algo)['kernel'] in RESUMABLE_KERNELS:
                 per_step = n_seg * (11 if mode == 'MOL' else model.n_classes) * 4
                 steps = max(1, min(T, getattr(model, 'noise_chunk_bytes', 2 << 30) // per_step))
                 steps = -(-T // (-(-T // steps)))            # equal slices (no short tail slice with its own launches)
@@ -339,7 +364,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for t0 in range(0, T, steps):
                     t1 = min(T, t0 + steps)
                     eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(t1 - t0), hop, algo=model.loop_algo, check=check, out=out_view,
-                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1), sparse_groups=groups)
+                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1), sparse_groups=groups, **lib_kw)
             except ResidencyError as e:
                 # the persistent grid was refused (on the first slice: a continuation cannot change kernels).  The other loop kernels read
                 # the up-sampled mel in full; the engine then degrades as usual on an unsliced call (one workgroup per CU, then the
@@ -351,7 +376,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for u in gens:
                     gens[u].manual_seed(int(seeds[u]))
                     burn_ctor_draws(model.rnn_dims, model.aux_dims, 'cpu', gens[u])
-                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view, sparse_groups=groups)
+                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view, sparse_groups=groups, **lib_kw)
             finally:
                 if pool is not None:
                     pool.shutdown()

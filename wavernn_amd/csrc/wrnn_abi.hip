@@ -17,6 +17,8 @@ hipError_t launch_cond_frames(const CondArgs &a, hipStream_t stream);
 hipError_t launch_cond_frames_slab(const CondArgs &a, hipStream_t stream);
 hipError_t launch_cond_frag(const CondArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_noise_mol(const float *in, float *out, long n, int B, int n_cus, hipStream_t stream);
+hipError_t launch_noise_fill(bool mol, int B, int C, int t0, int t1, uint64_t seed, const uint64_t *seg_id, float *out, int n_cus, hipStream_t stream);
+void noise_fill_host(bool mol, int B, int C, int t0, int t1, uint64_t seed, const uint64_t *seg_id, float *out);
 hipError_t launch_stream(const LoopArgs &args, int mode, hipStream_t stream);
 hipError_t launch_loop(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int loop_max_depth(int mode);
@@ -481,6 +483,7 @@ struct Plan {
 struct WsLayout {
     size_t status, xcc, segs, melc, c2f, c3f, c4f;
     size_t cI, npre;                    // stream kernel: whole-T conditioning; persistent kernels: one slab of derived MOL noise
+    size_t nlib;                        // wrnn_options.noise_lib: the noise the library draws, in the layout of `noise` -- one slab (persistent kernels) or all T steps
     size_t xbuf, state, cIf;            // loop kernel: exchange buffer, per-round state, conditioning slab
     size_t total;
 };
@@ -525,12 +528,18 @@ void plan_split(Plan *pl, int B, int ncl, int gmax, int depth)
 
 // steps per slab when the caller names none = what a slab holds: wrnn_loop_kernel -- the hoisted conditioning cI (2 KB per segment-step) + the
 // derived MoL noise; the slabbed kernels form cI in the loop: only the derived noise (44 B per segment-step)
-int default_slab(const Plan &pl, int mode)
+// wrnn_options.noise_lib, RAW on a slabbed kernel: the slab also holds its noise (C floats per segment-step) -- as much as fits NOISE_LIB_SLAB_BYTES
+constexpr size_t NOISE_LIB_SLAB_BYTES = (size_t)2 << 30;      // (the slice of noise WaveRNN.generate keeps resident when the caller draws it: noise_chunk_bytes)
+int default_slab(const Plan &pl, int mode, int C, bool noise_lib)
 {
     const int most = KINDS[pl.kind].slabbed ? 4096 : 1024;
     int slab = most;
     if (!KINDS[pl.kind].slabbed) slab = (int)((96u << 20) / ((size_t)pl.ngr_max * SEG * H * sizeof(float)));
     else if (mode == WRNN_MODE_MOL) slab = (int)((32u << 20) / ((size_t)pl.per_round * 11 * sizeof(float) * pl.rounds));
+    else if (noise_lib) {
+        const size_t fit = NOISE_LIB_SLAB_BYTES / ((size_t)pl.per_round * pl.rounds * C * sizeof(float));
+        slab = fit < (size_t)most ? (int)fit : most;
+    }
     return slab < 16 ? 16 : slab > most ? most : slab;
 }
 
@@ -559,6 +568,10 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     }
     if (o->sparse_groups < 0 || o->sparse_groups > sparse_max_slots()) {
         set_err("wrnn_options.sparse_groups = %d: 0 or 1 (one group per cluster) or 2", o->sparse_groups);
+        return WRNN_ERR_ARG;
+    }
+    if (o->noise_lib != 0 && o->noise_lib != 1) {
+        set_err("wrnn_options.noise_lib = %d: 0 (the caller's `noise`) or 1 (the library draws it)", o->noise_lib);
         return WRNN_ERR_ARG;
     }
     const bool two_groups = o->sparse_groups == 2;
@@ -642,7 +655,7 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     if (k.persistent) {
         if (two_groups) plan_split(pl, B, ncl, sparse_max_slots(), sparse_max_slots());      // depth 2, rounds = ceil(groups / 32)
         else plan_split(pl, B, ncl, k.max_depth(p->mode), o->depth);
-        pl->slab = o->slab_steps >= 1 ? o->slab_steps : default_slab(*pl, p->mode);      // (an explicit slab length is taken as given -- short slabs included: tests)
+        pl->slab = o->slab_steps >= 1 ? o->slab_steps : default_slab(*pl, p->mode, p->C, o->noise_lib != 0);      // (an explicit slab length is taken as given -- short slabs included: tests)
         if (pl->slab > T) pl->slab = T;
         pl->tab_fps = DUO_TAB_FPS;
     } else if (partial) {
@@ -658,8 +671,10 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     return WRNN_OK;
 }
 
-WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int n_frames)
+// noise_lib: the call draws its own noise (wrnn_options.noise_lib) -- appended, so that every other offset is what it is without
+WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int n_frames, bool noise_lib)
 {
+    const size_t noise_row = (size_t)B * (p->mode == WRNN_MODE_MOL ? 11 : p->C) * sizeof(float);      // one step of `noise`
     const KindDesc &k = KINDS[pl.kind];
     WsLayout l;
     memset(&l, 0, sizeof l);
@@ -668,7 +683,11 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
     l.xcc = o;    o = al(o + XCC_WORDS * sizeof(unsigned));
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
-    if (pl.kind == K_GENERIC) { l.total = o; return l; }
+    if (pl.kind == K_GENERIC) {
+        l.nlib = o; if (noise_lib) o = al(o + (size_t)T * noise_row);
+        l.total = o;
+        return l;
+    }
     // per-frame aux tables: one row per frame of the call's conditioning (+ the zero row) -- or, for a slabbed kernel, per SEGMENT and
     // slab: (slab - 1) / hop + 2 rows per segment (+ the zero row), refilled for every slab: independent of the corpus' length
     const size_t tab_rows = k.slabbed ? (size_t)B * pl.tab_fps + 1 : (size_t)n_frames + 1;
@@ -684,6 +703,7 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
         l.cI = o;    o = al(o + (size_t)T * B * H * sizeof(float));
         l.npre = o;
     }
+    l.nlib = o;   if (noise_lib) o = al(o + (size_t)(k.persistent ? pl.slab : T) * noise_row);
     l.total = o;
     return l;
 }
@@ -745,7 +765,7 @@ int plan_report(const wrnn_plan_traits *tr, int B, int T, int n_frames, const wr
         out->kernel = KINDS[pl.kind].name; out->units_per_wg = KINDS[pl.kind].units_per_wg;
         out->clusters = pl.ncl; out->depth = pl.G; out->rounds = pl.rounds; out->slab_steps = pl.slab;
     }
-    if (ws_bytes) *ws_bytes = ws_layout(tr, pl, B, T, n_frames).total;
+    if (ws_bytes) *ws_bytes = ws_layout(tr, pl, B, T, n_frames, o.noise_lib != 0).total;
     return WRNN_OK;
 }
 }  // namespace
@@ -776,20 +796,26 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
                                       const float *mels_up, const float *aux, const float *noise, float *out,
                                       void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream_)
 {
-    if (!p || !mels_up || !aux || !noise || !out || !workspace) { set_err("NULL argument"); return WRNN_ERR_ARG; }
+    const wrnn_options opts = norm_struct(opt), *o = &opts;
+    const bool lib_noise = o->noise_lib == 1;       // (any other value but 0: make_plan refuses it)
+    if (lib_noise && noise) {
+        set_err("wrnn_options.noise_lib = 1: the library draws the noise itself -- `noise` must be NULL (the tensor passed would not be read)");
+        return WRNN_ERR_ARG;
+    }
+    if (!p || !mels_up || !aux || (!noise && !lib_noise) || !out || !workspace) { set_err("NULL argument"); return WRNN_ERR_ARG; }
     int rc = check_segments(B, T, seg_pos, seg_lim, L, hop, n_frames);
     if (rc != WRNN_OK) return rc;
-    const wrnn_options opts = norm_struct(opt), *o = &opts;
     Plan pl;      // (kernel, split and workspace layout do not depend on the step range: a continuation lands on the whole call's)
     if ((rc = make_plan(&p->tr, B, T, o, &pl)) != WRNN_OK) return rc;
     const KindDesc &k = KINDS[pl.kind];
-    const WsLayout l = ws_layout(&p->tr, pl, B, T, n_frames);
+    const WsLayout l = ws_layout(&p->tr, pl, B, T, n_frames, lib_noise);
     if (workspace_bytes < l.total) { set_err("workspace %zu < required %zu", workspace_bytes, l.total); return WRNN_ERR_WORKSPACE; }
     if (((uintptr_t)workspace & 255) != 0) { set_err("workspace must be 256-byte aligned"); return WRNN_ERR_ARG; }
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard dg(p->device);
     HIPCHK(dg.err);
     char *ws = (char *)workspace;
+    const bool mol_mode = p->tr.mode == WRNN_MODE_MOL;
     wrnn_timer *timer = o->timer;
     if (timer && pl.t0 == 0) timer->used = 0;            // a continuing call (t_begin > 0) adds its launches to the same total
 
@@ -839,6 +865,10 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         g.fc1T = p->g_fc1T; g.fc1_b = p->fc1_b; g.fc2T = p->g_fc2T; g.fc2_b = p->fc2_b; g.fc3T = p->fc3T; g.fc3_b = p->fc3_b;
         g.mels_up = mels_up; g.aux = aux; g.noise = noise; g.force_x = o->force_x; g.out = out; g.dbg_logits = o->logits;
         g.seg_pos = d_pos; g.seg_lim = d_lim;
+        if (lib_noise) {
+            HIPCHK(launch_noise_fill(mol_mode, B, p->tr.C, 0, T, o->noise_seed, o->noise_seg_id, (float *)(ws + l.nlib), p->tr.n_cus, stream));
+            g.noise = (const float *)(ws + l.nlib);
+        }
         g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         HIPCHK(launch_generic(g, p->tr.mode, stream));
@@ -900,9 +930,16 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         c.cI = (float *)(ws + l.cIf);
         for (int s0 = pl.t0; s0 < pl.t1; s0 += pl.slab) {
             const int s1 = s0 + pl.slab < pl.t1 ? s0 + pl.slab : pl.t1;
+            // wrnn_options.noise_lib: this slab's noise, drawn into the workspace in front of its launches -- what the caller's tensor holds in rows
+            // [s0 - t_begin, s1 - t_begin)
+            if (lib_noise) HIPCHK(launch_noise_fill(mol, B, p->tr.C, s0, s1, o->noise_seed, o->noise_seg_id, (float *)(ws + l.nlib), p->tr.n_cus, stream));
             if (mol) {   // noise rows are relative to t_begin (wrnn_options.t_begin)
-                HIPCHK(launch_noise_mol(noise + (size_t)(s0 - pl.t0) * 11 * B, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->tr.n_cus, stream));
+                const float *const rows = lib_noise ? (const float *)(ws + l.nlib) : noise + (size_t)(s0 - pl.t0) * 11 * B;
+                HIPCHK(launch_noise_mol(rows, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->tr.n_cus, stream));
                 a.noise_pre = (const float *)(ws + l.npre);
+                a.noise_t0 = s0;
+            } else if (lib_noise) {
+                a.noise = (const float *)(ws + l.nlib);
                 a.noise_t0 = s0;
             } else {
                 a.noise_t0 = pl.t0;
@@ -946,6 +983,10 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         c.cI = (float *)(ws + l.cI);
         a.cI = c.cI;
         HIPCHK(launch_cond(c, p->tr.n_cus, o->cond_valu != 0, stream));
+        if (lib_noise) {
+            HIPCHK(launch_noise_fill(mol_mode, B, p->tr.C, 0, T, o->noise_seed, o->noise_seg_id, (float *)(ws + l.nlib), p->tr.n_cus, stream));
+            a.noise = (const float *)(ws + l.nlib);
+        }
         a.b0 = 0;
         a.nb = B;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
@@ -997,7 +1038,7 @@ extern "C" int wrnn_debug_read_exchange(const wrnn_pack *p, void *workspace, int
         set_err("no such exchange layer");
         return WRNN_ERR_ARG;
     }
-    const WsLayout l = ws_layout(&p->tr, pl, n_segments, T, n_frames);
+    const WsLayout l = ws_layout(&p->tr, pl, n_segments, T, n_frames, whole.noise_lib != 0);
     HIPCHK(hipDeviceSynchronize());
     std::vector<float> frag((size_t)SEG * H);
     const size_t off = ((((size_t)cluster * LMAXG + slot) * NXLAYER + layer) * XRING + ring) * SEG * H;
@@ -1007,6 +1048,40 @@ extern "C" int wrnn_debug_read_exchange(const wrnn_pack *p, void *workspace, int
             const int w = k >> 7, r = (k >> 4) & 7, kq = (k >> 2) & 3, e = k & 3;
             host_out[(size_t)j * H + k] = frag[(size_t)(((w * 8 + r) * 64 + kq * 16 + j) * 4 + e)];
         }
+    return WRNN_OK;
+}
+
+namespace {
+int check_noise_fill(int mode, int32_t B, int32_t C, int32_t t0, int32_t t1, const float *out)
+{
+    if (mode != WRNN_MODE_MOL && mode != WRNN_MODE_RAW) { set_err("unknown mode %d", mode); return WRNN_ERR_ARG; }
+    if (!out) { set_err("NULL argument"); return WRNN_ERR_ARG; }
+    if (B < 1 || t0 < 0 || t1 <= t0 || (mode == WRNN_MODE_RAW && C < 1)) { set_err("bad noise shape: %d segments, %d classes, steps [%d, %d)", B, C, t0, t1); return WRNN_ERR_ARG; }
+    if ((double)(t1 - t0) * B >= 2147483648.0) { set_err("%d steps x %d segments: more than 2^31 - 1 rows in one fill; split the step range", t1 - t0, B); return WRNN_ERR_ARG; }
+    return WRNN_OK;
+}
+}  // namespace
+
+extern "C" int wrnn_noise_fill(int mode, int32_t n_segments, int32_t n_classes, int32_t t_begin, int32_t t_end, uint64_t seed, const uint64_t *seg_id,
+                               float *out, int device, void *stream)
+{
+    int rc = check_noise_fill(mode, n_segments, n_classes, t_begin, t_end, out);
+    if (rc != WRNN_OK) return rc;
+    if (((uintptr_t)out & 15) != 0) { set_err("`out` must be 16-byte aligned"); return WRNN_ERR_ARG; }
+    const int cus = wrnn_device_cus(device);
+    if (cus < 0) return cus;
+    DeviceGuard dg(device);
+    HIPCHK(dg.err);
+    HIPCHK(launch_noise_fill(mode == WRNN_MODE_MOL, n_segments, n_classes, t_begin, t_end, seed, seg_id, out, cus, (hipStream_t)stream));
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_noise_fill_host(int mode, int32_t n_segments, int32_t n_classes, int32_t t_begin, int32_t t_end, uint64_t seed, const uint64_t *seg_id,
+                                    float *out)
+{
+    const int rc = check_noise_fill(mode, n_segments, n_classes, t_begin, t_end, out);
+    if (rc != WRNN_OK) return rc;
+    noise_fill_host(mode == WRNN_MODE_MOL, n_segments, n_classes, t_begin, t_end, seed, seg_id, out);
     return WRNN_OK;
 }
 

@@ -136,7 +136,7 @@ class LoopEngine:
         seg_lim = np.full(B, L, dtype=np.int32)
         return self.run_segments(mels_up, aux, seg_pos, seg_lim, T, noise, hop, **kw)
 
-    def options(self, algo='auto', depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, tuning=0, sparse_groups=0):
+    def options(self, algo='auto', depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, tuning=0, sparse_groups=0, noise_lib=False):
         if algo == 'auto' and self._auto_floor is not None:      # (after a refused cooperative launch: see run_segments)
             algo = self._auto_floor
         o = _lib.Options()
@@ -144,6 +144,7 @@ class LoopEngine:
         o.depth, o.clusters, o.slab_steps, o.cond_valu = int(depth), int(clusters), int(slab_steps), int(bool(cond_valu))
         o.tuning = int(tuning)
         o.sparse_groups = int(sparse_groups or 0)      # wrnn_sparse_kernel: 2 = two groups per cluster (on request; any other kernel refuses it)
+        o.noise_lib = int(bool(noise_lib))             # the library draws the sampling noise (a slab of it joins the workspace; may shorten a RAW slab)
         if t_range is not None:
             o.t_begin, o.t_end = int(t_range[0]), int(t_range[1])
         return o
@@ -161,7 +162,7 @@ class LoopEngine:
 
     def run_segments(self, mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo='auto', force_x=None, want_logits=False,
                      check=True, depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, out=None, logits=None,
-                     phase_clocks=None, tuning=0, progress=None, sparse_groups=0, _fallback=False):
+                     phase_clocks=None, tuning=0, progress=None, sparse_groups=0, noise_seed=0, noise_seg_id=None, _fallback=False):
         """mels_up (L,feat) / aux (n_frames,4*aux_dims) / noise: float32 CUDA tensors; seg_pos / seg_lim: host
         int32 arrays (B,) -- segment b, step t reads position seg_pos[b]+t, zero conditioning from seg_lim[b] on
         (several utterances: concatenated conditioning).  Returns out (B,T) CUDA [and logits (T,B,C)].
@@ -172,11 +173,15 @@ class LoopEngine:
         steps; t0 > 0 continues the previous call on this engine's workspace (pass the same `out`; `noise` then holds the
         rows of [t0, t1) only) -- how long RAW runs draw their noise in chunks instead of T*B*C floats at once.
         progress: optional `f(steps_done, T, n_segments)` called from a HIP runtime thread when the device has finished each
-        conditioning slab (wrnn_options.progress; must not touch the device)."""
+        conditioning slab (wrnn_options.progress; must not touch the device).
+        noise=None: the library draws the noise itself (wrnn_options.noise_lib), slab by slab on the stream, from the counter-based generator
+        keyed by `noise_seed`; noise_seg_id: one 64-bit stream id per segment (None: segment b has id b).  The samples are those of the same
+        call fed `rng.library_noise(...)`; a continued call (t_range) needs nothing but the same seed and ids."""
         rows_in = mels_up if isinstance(mels_up, MelRows) else None
         if rows_in is not None:
             mels_up = rows_in.rows
-        for name, t_ in (('mels_up', mels_up), ('aux', aux), ('noise', noise)):
+        lib_noise = noise is None
+        for name, t_ in (('mels_up', mels_up), ('aux', aux)) + (() if lib_noise else (('noise', noise),)):
             if not (t_.is_cuda and t_.dtype == torch.float32 and t_.is_contiguous()):
                 raise ValueError(f'{name} must be a contiguous float32 CUDA tensor')
         seg_pos = np.ascontiguousarray(seg_pos, dtype=np.int32)
@@ -193,10 +198,17 @@ class LoopEngine:
             # one on that slice only; the two kernels keep different state / ring layouts -- the library also checks: status word 8)
             algo = self._slice_algo
         need = (t1 - t0) * 11 * B if self.mode == 'MOL' else (t1 - t0) * B * self.n_classes
-        if noise.numel() != need:
+        if not lib_noise and noise.numel() != need:
             raise ValueError(f'noise has {noise.numel()} elements, expected {need}')
         n_frames = int(aux.shape[0])
-        o = self.options(algo, depth, clusters, slab_steps, cond_valu, t_range, tuning, sparse_groups)
+        o = self.options(algo, depth, clusters, slab_steps, cond_valu, t_range, tuning, sparse_groups, lib_noise)
+        if lib_noise:                     # (the id array is a host array read during the call only)
+            o.noise_seed = int(noise_seed) & (2 ** 64 - 1)
+            if noise_seg_id is not None:
+                noise_seg_id = np.ascontiguousarray(noise_seg_id, dtype=np.uint64)
+                if noise_seg_id.shape != (B,):
+                    raise ValueError('noise_seg_id: one 64-bit id per segment')
+                o.noise_seg_id = noise_seg_id.ctypes.data
         nbytes = int(self.lib.wrnn_workspace_bytes_segments(self._pack, B, T, n_frames, ctypes.byref(o)))
         if nbytes == 0:
             raise _lib.WrnnError('bad geometry / options: ' + self.lib.wrnn_last_error().decode())
@@ -229,7 +241,7 @@ class LoopEngine:
             o.mel_taps, o.seg_moff = rows_in.taps.ctypes.data, seg_moff.ctypes.data
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.wrnn_generate_segments(self._pack, B, T, seg_pos.ctypes.data, seg_lim.ctypes.data, L, hop, n_frames,
-                                             mels_up.data_ptr(), aux.data_ptr(), noise.data_ptr(), out.data_ptr(),
+                                             mels_up.data_ptr(), aux.data_ptr(), None if lib_noise else noise.data_ptr(), out.data_ptr(),
                                              self._ws.data_ptr(), self._ws.numel(), ctypes.byref(o), stream)
         if rc == _lib.ERR_RESIDENCY and t0 == 0 and (algo == 'auto' or _fallback):
             # the persistent grid is not co-resident right now (CU masking, a smaller partition, another cooperative kernel).  `auto`
@@ -252,7 +264,7 @@ class LoopEngine:
                     self._progress_keep.pop()       # (the retry registers its own thunk)
                 res = self.run_segments(mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo=nxt, depth=depth, clusters=clusters, force_x=force_x,
                                         want_logits=want_logits, check=check, slab_steps=slab_steps, cond_valu=cond_valu, t_range=t_range, out=out,
-                                        logits=logits, phase_clocks=phase_clocks, tuning=tuning, progress=progress, _fallback=True)      # (sparse_groups: wrnn_sparse_kernel's alone -- dropped)
+                                        logits=logits, phase_clocks=phase_clocks, tuning=tuning, progress=progress, noise_seed=noise_seed, noise_seg_id=noise_seg_id, _fallback=True)      # (sparse_groups: wrnn_sparse_kernel's alone -- dropped)
                 if algo == 'auto':
                     self._auto_floor = self._auto_floor or nxt       # later `auto` calls start from the kernel that ran (no refused launch + workspace re-allocation per call)
                 return res
@@ -264,7 +276,7 @@ class LoopEngine:
                     self._auto_floor = 'stream'
                 return self.run_segments(mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo='stream', force_x=force_x,
                                          want_logits=want_logits, check=check, slab_steps=slab_steps, cond_valu=cond_valu, out=out, logits=logits,
-                                         phase_clocks=phase_clocks, tuning=tuning, progress=progress)
+                                         phase_clocks=phase_clocks, tuning=tuning, progress=progress, noise_seed=noise_seed, noise_seg_id=noise_seg_id)
             # ... the same refusal on the first slice of a step-sliced run (only the loop kernels continue a call): the caller, who owns
             # the slicing and the noise stream, redoes the whole call on the stream kernel
             raise _lib.ResidencyError('cooperative launch refused (' + why + ')')
@@ -272,7 +284,7 @@ class LoopEngine:
         self._launches = (self._launches if t0 > 0 else 0) + int(self._info.launches)
         if t0 == 0:
             self._slice_algo = KERNEL_ALGOS.get((self._info.kernel or b'').decode(), (None, None))[0]
-        self._last_opts = (B, T, n_frames, self.options(algo, depth, clusters, slab_steps, cond_valu, None, 0, sparse_groups))
+        self._last_opts = (B, T, n_frames, self.options(algo, depth, clusters, slab_steps, cond_valu, None, 0, sparse_groups, lib_noise))
         if check:
             rc = self.lib.wrnn_status(self._ws.data_ptr(), stream)      # synchronises the stream: every queued progress call has run
             del self._progress_keep[:]

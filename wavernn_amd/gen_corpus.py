@@ -8,7 +8,8 @@ gen_wavernn.py:38-65).  All utterances are folded into one segment table (`batch
 one contiguous block per rank, each rank runs ONE loop launch, the finished audio is all-gathered (RCCL) and every rank
 writes the WAVs of the utterances whose first segment it owned.  `--seed S` gives utterance u the parity noise stream of
 `torch.manual_seed(S + u)` (equal to a per-utterance `generate()` call with that seed); without it noise is drawn on the
-device.
+device.  `--noise library --seed S`: the loop draws its noise itself, utterance u under seed S + u (equal to
+`gen_wavernn --noise library --seed S+u`, whatever the batch and the rank count; no noise crosses the host).
 """
 import argparse
 import os
@@ -48,10 +49,14 @@ def main(argv=None):
     ap.add_argument('--target', '-t', type=int, default=11000)
     ap.add_argument('--overlap', '-o', type=int, default=550)
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
-    ap.add_argument('--seed', type=int, default=None, help='parity noise: utterance u uses torch.manual_seed(seed + u)')
+    ap.add_argument('--seed', type=int, default=None, help='parity noise: utterance u uses torch.manual_seed(seed + u); --noise library: its stream seed')
+    ap.add_argument('--noise', choices=['cpu', 'device', 'library'], default=None,
+                    help='where the sampling noise comes from (default: cpu with --seed, else device); cpu and library need --seed')
     ap.add_argument('--sparse-groups', type=int, default=None, choices=[1, 2],
                     help='a pruned MoL model on wrnn_sparse_kernel: groups of segments per cluster (2: 512 segments a round; a dense model ignores it)')
     a = ap.parse_args(argv)
+    if a.noise in ('cpu', 'library') and a.seed is None:
+        ap.error(f'--noise {a.noise} needs --seed')
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -72,7 +77,7 @@ def main(argv=None):
     paths, mels = load_mels(a.mels)
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
     outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group,
-                           noise_source='cpu' if seeds is not None else 'device', finish='own')
+                           noise_source=a.noise or ('cpu' if seeds is not None else 'device'), finish='own')
     out_dir = Path(a.output)
     out_dir.mkdir(parents=True, exist_ok=True)
     n = 0

@@ -51,7 +51,10 @@ def main(argv=None):
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--output', default='.', help='output directory')
     ap.add_argument('--seed', type=int, default=None)
-    ap.add_argument('--device-noise', action='store_true', help='draw sampling noise on the GPU (not comparable with a CPU run)')
+    ap.add_argument('--device-noise', action='store_true', help='draw sampling noise on the GPU (not comparable with a CPU run); the same as --noise device')
+    ap.add_argument('--noise', choices=['cpu', 'device', 'library'], default=None,
+                    help="cpu (default): the reference's CPU stream after torch.manual_seed(--seed); device: torch's device generator; library: drawn inside "
+                         'the loop from a counter-based generator -- the utterance sounds the same alone and in any gen_corpus batch with the same seed')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -59,10 +62,12 @@ def main(argv=None):
     model = WaveRNN(**SHIPPED, mode=a.mode).to('cuda')
     if a.weights:
         model.load(a.weights)
-    if a.device_noise:
-        model.noise_source = 'device'
+    if a.device_noise and a.noise not in (None, 'device'):
+        ap.error('--device-noise contradicts --noise ' + a.noise)
+    model.noise_source = 'device' if a.device_noise else (a.noise or 'cpu')
     if a.seed is not None:
         torch.manual_seed(a.seed)
+        model.noise_seed = a.seed
     out, path = gen_from_file(model, Path(a.file).expanduser().resolve(), Path(a.output), a.batched, a.target, a.overlap)
     n = out.shape[0]
     print(f'{path}: {n} samples ({n / model.sample_rate:.2f} s), loop {model.last_loop_kernel} {model.last_loop_ms:.1f} ms '

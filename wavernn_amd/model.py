@@ -127,8 +127,16 @@ class WaveRNN(nn.Module):
         self.num_params()
 
         #: 'cpu' = consume torch's global CPU generator exactly like the reference's CPU run (parity);
-        #: 'device' = device Philox generator (what the reference does when it runs on a GPU)
+        #: 'device' = device Philox generator (what the reference does when it runs on a GPU);
+        #: 'library' = the loop draws its noise itself (wrnn_options.noise_lib: a counter-based generator inside libwavernn_amd.so, slab by slab on the
+        #: stream): ONE engine call for all T steps, no `noise_chunk_bytes` slices, no noise tensor, torch's generators untouched.  A segment's noise is
+        #: a function of (noise_key, its stream id, step, index) alone -- id = `batch.library_seg_ids(noise_seed, folds)` -- so an utterance sounds the same
+        #: alone and in any `generate_corpus` batch, chunk or shard given the same seed.  Not comparable with the reference's CPU run ('cpu' is).
         self.noise_source = 'cpu'
+        #: noise_source='library': the utterance's seed (what `seeds[u]` is to generate_corpus; its low 32 bits count) ...
+        self.noise_seed = 0
+        #: ... and the generator's key (wrnn_options.noise_seed), shared by every call of this model
+        self.noise_key = 0
         #: 'auto' | 'loop' | 'sparse' | 'stream'  (WRNN_ALGO_*, include/wavernn_amd.h)
         self.loop_algo = 'auto'
         #: 2 = a run planned on wrnn_sparse_kernel puts TWO groups of <= 16 segments on each of its 16 clusters (wrnn_options.sparse_groups: 512 segments a
@@ -311,7 +319,7 @@ class WaveRNN(nn.Module):
             # continuing the loop where the previous one stopped (wrnn_options.t_begin / t_end)
             per_step = B * (11 if self.mode == 'MOL' else self.n_classes) * 4
             resumable = eng.plan(B, T, algo=self.loop_algo)['kernel'] in RESUMABLE_KERNELS
-            chunk = max(1, min(T, self.noise_chunk_bytes // per_step)) if resumable else T
+            chunk = max(1, min(T, self.noise_chunk_bytes // per_step)) if (resumable and self.noise_source != 'library') else T
             chunk = -(-T // (-(-T // chunk)))                # equal slices (no short tail slice with its own launches)
             rng_state = torch.get_rng_state() if (self.noise_source == 'cpu' and (chunk < T or rows)) else None
             algo = self.loop_algo
@@ -370,6 +378,10 @@ class WaveRNN(nn.Module):
         if self.progress_callback is not None:
             t_start, cb = time.perf_counter(), self.progress_callback
             prog = lambda done, T_, n_: cb(done, T_, n_, time.perf_counter() - t_start)
+        if self.noise_source == 'library':       # the loop draws its own noise: one call, nothing to slice
+            from .batch import library_seg_ids
+            return eng.run(mels_up, aux, B, T, stride, None, self.hop_length, algo=algo, progress=prog, sparse_groups=sparse_groups,
+                           noise_seed=self.noise_key, noise_seg_id=library_seg_ids(self.noise_seed, B))
         for t0 in range(0, T, chunk):
             t1 = min(T, t0 + chunk)
             noise = draw_steps(self.mode, B, t1 - t0, self.n_classes, device, self.noise_source)
