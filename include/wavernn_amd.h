@@ -425,6 +425,38 @@ int wrnn_taco_decode(int device, const wrnn_taco_weights *w, const wrnn_taco_cal
 int wrnn_taco_status(const void *workspace, unsigned *out4, void *stream);
 const char *wrnn_taco_last_error(void);
 
+/*
+ * The decoder loop for a LIST of sentences in one launch (csrc/wrnn_taco_batch.hip, wrnn_taco_batch_kernel): the register-resident kernel of
+ * variant 2 with a sentence dimension -- each layer of a step runs for every live sentence before the next layer, so a step costs its ten
+ * exchange hops once, not once per sentence.  Sentence s decodes until its own stop test (:411) fires or it has run max_steps[s] steps; rows
+ * of mel_out[s] / scores_out[s] past steps_done[s] are not touched.  mel_out[s], scores_out[s] and steps_done[s] are bit-identical to
+ * wrnn_taco_decode(variant = 2) on that sentence alone.  Limits: 1..WRNN_TACO_BATCH_MAX sentences per call, 1..WRNN_TACO_BATCH_NMAX encoder
+ * positions per sentence (longer sentences: wrnn_taco_decode), r <= 8, a device with >= 128 CUs (else WRNN_ERR_RESIDENCY: there is no
+ * flag-barrier form of this kernel).  The arrays marked HOST are read during the call only.
+ */
+#define WRNN_TACO_BATCH_MAX 8
+#define WRNN_TACO_BATCH_NMAX 256
+typedef struct wrnn_taco_batch_call {
+    uint32_t struct_bytes;
+    int32_t n_sent;                    /* 1..WRNN_TACO_BATCH_MAX */
+    int32_t r, max_r;                  /* as wrnn_taco_call */
+    float stop_threshold;              /* :411 */
+    const int32_t *n;                  /* HOST [n_sent]: encoder positions, 1..WRNN_TACO_BATCH_NMAX */
+    const int32_t *max_steps;          /* HOST [n_sent]: per-sentence step limit (>= 1) */
+    const float *const *seq, *const *seq_proj;   /* HOST [n_sent] of DEVICE [n_s][256] */
+    float *const *mel_out;             /* HOST [n_sent] of DEVICE [max_steps_s][n_mels][r] */
+    float *const *scores_out;          /* HOST [n_sent] of DEVICE [max_steps_s][n_s] */
+    int32_t *steps_done;               /* DEVICE [n_sent]: decoder steps run per sentence */
+    void *workspace;                   /* wrnn_taco_batch_workspace_bytes(n_sent) */
+    size_t workspace_bytes;
+    void *stream;
+} wrnn_taco_batch_call;
+/* 0 for an n_sent outside 1..WRNN_TACO_BATCH_MAX. */
+size_t wrnn_taco_batch_workspace_bytes(int32_t n_sent);
+/* Asynchronous on `stream`.  Every argument is validated before the device is touched (WRNN_ERR_ARG; wrnn_taco_last_error() names the sentence
+ * and the limit).  wrnn_taco_status reads this workspace as it reads wrnn_taco_decode's. */
+int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c);
+
 /* The bidirectional GRU that ends a CBHG (reference models/tacotron.py:95, applied at :137: `x, _ = self.rnn(x)`), one sequence,
  * hidden size 128 (encoder and post-net of the reference's hparams): one persistent workgroup per direction with W_hh in
  * registers.  gi_* = W_ih x + b_ih for all frames (a plain GEMM: the caller's).  Errors: wrnn_taco_last_error(). */

@@ -28,7 +28,7 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
-           'wrnn_taco_encode', 'wrnn_taco_postnet']
+           'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch']
 
 
 class Weights(ctypes.Structure):
@@ -62,6 +62,19 @@ class TacoCall(ctypes.Structure):
                 ('max_steps', ctypes.c_int32), ('stop_threshold', ctypes.c_float), ('seq', ctypes.c_void_p), ('seq_proj', ctypes.c_void_p),
                 ('mel_out', ctypes.c_void_p), ('scores_out', ctypes.c_void_p), ('steps_done', ctypes.c_void_p),
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p), ('variant', ctypes.c_int32)]
+
+
+TACO_BATCH_MAX = 8           # WRNN_TACO_BATCH_MAX: sentences per wrnn_taco_decode_batch call
+TACO_BATCH_NMAX = 256        # WRNN_TACO_BATCH_NMAX: encoder positions per sentence in that call
+
+
+class TacoBatchCall(ctypes.Structure):
+    """wrnn_taco_batch_call: n / max_steps / seq / seq_proj / mel_out / scores_out point to HOST arrays of n_sent entries."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('n_sent', ctypes.c_int32), ('r', ctypes.c_int32), ('max_r', ctypes.c_int32),
+                ('stop_threshold', ctypes.c_float), ('n', ctypes.POINTER(ctypes.c_int32)), ('max_steps', ctypes.POINTER(ctypes.c_int32)),
+                ('seq', ctypes.POINTER(ctypes.c_void_p)), ('seq_proj', ctypes.POINTER(ctypes.c_void_p)),
+                ('mel_out', ctypes.POINTER(ctypes.c_void_p)), ('scores_out', ctypes.POINTER(ctypes.c_void_p)),
+                ('steps_done', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
 
 
 class BigruCall(ctypes.Structure):
@@ -220,6 +233,9 @@ def lib():
     L.wrnn_taco_decode.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoCall)]
     L.wrnn_taco_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32 * 4), ctypes.c_void_p]
     L.wrnn_taco_last_error.restype = ctypes.c_char_p
+    L.wrnn_taco_batch_workspace_bytes.argtypes = [ctypes.c_int32]
+    L.wrnn_taco_batch_workspace_bytes.restype = ctypes.c_size_t
+    L.wrnn_taco_decode_batch.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoBatchCall)]
     L.wrnn_bigru.argtypes = [ctypes.c_int, ctypes.POINTER(BigruCall)]
     L.wrnn_taco_front_create.argtypes = [ctypes.POINTER(TacoFrontWeights), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_taco_front_destroy.argtypes = [ctypes.c_void_p]

@@ -29,25 +29,10 @@
 
 #include "../../include/wavernn_amd.h"
 #include "wrnn_device.h"
+#include "wrnn_taco.h"
 
 namespace wrnn {
 
-constexpr int T_NM = 80;        // mel channels
-constexpr int T_P1 = 256;       // prenet fc1
-constexpr int T_P2 = 128;       // prenet fc2
-constexpr int T_DD = 256;       // decoder dims (attention GRU hidden) == encoder sequence width (context)
-constexpr int T_LD = 512;       // LSTM dims
-constexpr int T_AF = 32;        // attention location filters
-constexpr int T_AK = 31;        // ... their taps
-constexpr int T_NMAX = 1024;    // encoder positions the workspace is laid out for
-constexpr int T_MAXWG = 128;
-
-// workspace (floats)
-constexpr int A_PRE_IN = 0, A_PRE1 = 128, A_PRE2 = 384, A_ATTN_H = 512 /* [2][256] */, A_CTX = 1024, A_PQ = 1280,
-              A_S = 1536 /* [NMAX] */, A_CUM = 2560, A_ATT = 3584, A_X = 4608, A_X2 = 5120, A_X3 = 5632,
-              A_H1 = 6144 /* [2][512] */, A_H2 = 7168, A_C1 = 8192, A_C2 = 8704, A_END = 9216;
-// then (unsigned) [T_MAXWG] arrival words, [T_MAXWG] not-below-threshold counts, [8] status
-constexpr int U_FLAG = 0, U_CNT = T_MAXWG, U_STATUS = 2 * T_MAXWG, U_END = 2 * T_MAXWG + 8;
 
 struct TacoArgs {
     wrnn_taco_weights w;
@@ -63,7 +48,6 @@ struct TacoArgs {
 };
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }      // (DPP / permlane-swap butterflies, wrnn_device.h: the same tree as the __shfl_xor loop, without the LDS crossbar)
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // dot(w[0..K), x[0..K)) with K a multiple of 4: lanes take float4 chunks round-robin; x in LDS.  Result in every lane.
 __device__ __forceinline__ float row_dot(const float *__restrict__ wrow, const float *x, int K, int lane)
@@ -328,8 +312,6 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_decoder_kernel(const TacoArgs
 // (Hardware exp / rcp in the gate functions were measured -- profiles/r03ac_taco_profile.json: 28.5 -> 26.6 us per step -- and
 // NOT kept: the error against the CPU mirror of the reference grew from 5e-9 to 2e-5 over 200 frames for 0.7 % of config 3.)
 // =================================================================================================================================
-constexpr int R_NWG = 128, R_NWV = R_NWG * NW;
-constexpr int R_MAXR = 8;
 // (Measured and dropped in round 3, profiles/r03aj_taco_profile_local_prenet.json: both PreNet layers computed by every workgroup that owns
 // attention-GRU units for itself -- two exchange hops less, but 80 KB of LDS and 128 registers per thread more: no faster.)
 // tagged vectors: offsets in 8-byte entries, [2 parity buffers][length]
@@ -337,30 +319,6 @@ constexpr int VL_MEL = T_NM * R_MAXR, VL_S = T_NMAX;
 constexpr int V_MEL = 0, V_PRE1 = V_MEL + 2 * VL_MEL, V_PRE2 = V_PRE1 + 2 * T_P1, V_ATTNH = V_PRE2 + 2 * T_P2, V_CTX = V_ATTNH + 2 * T_DD,
               V_PQ = V_CTX + 2 * T_DD, V_S = V_PQ + 2 * T_DD, V_X = V_S + 2 * VL_S, V_X2 = V_X + 2 * T_LD, V_X3 = V_X2 + 2 * T_LD,
               V_H1 = V_X3 + 2 * T_LD, V_H2 = V_H1 + 2 * T_LD, V_END = V_H2 + 2 * T_LD;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float lane_get(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-// sum over the 64 lanes, in every lane: quad xor 1, xor 2, half-row mirror, row mirror (16-lane row totals), then the four rows
-__device__ __forceinline__ float wave_total(float v)
-{
-    v += dpp_get<0xB1>(v);
-    v += dpp_get<0x4E>(v);
-    v += dpp_get<0x141>(v);
-    v += dpp_get<0x140>(v);
-    return (lane_get(v, 0) + lane_get(v, 16)) + (lane_get(v, 32) + lane_get(v, 48));
-}
-__device__ __forceinline__ float4 ldw4(const float *w, bool on) { return on ? *reinterpret_cast<const float4 *>(w) : make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float fma4(const float4 a, const float *x, float s)
-{
-    const float4 b = *reinterpret_cast<const float4 *>(x);
-    s = fmaf(a.x, b.x, s); s = fmaf(a.y, b.y, s); s = fmaf(a.z, b.z, s); s = fmaf(a.w, b.w, s);
-    return s;
-}
 
 // PROF: workgroup 0, thread 0 accumulates shader clocks per layer, [2 L - 2] = until its input is staged, [2 L - 1] = compute + publish
 // (L = 1 .. 10), [20] = steps; flushed to the 24 words after the tagged vectors (read by scripts/gpu_taco_profile.py)

@@ -1,0 +1,635 @@
+// wrnn_taco_batch.hip -- wrnn_taco_batch_kernel: the register-resident Tacotron decoder loop of wrnn_taco.hip (wrnn_taco_resident_kernel) for up
+// to WRNN_TACO_BATCH_MAX sentences in ONE cooperative launch (`wrnn_taco_decode_batch`).  A list of sentences (BASELINE config 3 reads six) is
+// otherwise decoded one launch after the other, each step of each sentence paying ten dependent exchange hops on its own.
+//
+// Same grid (128 co-resident workgroups x 4 waves), same ownership (wave gw owns row / unit gw of every layer, lanes split K), same resident
+// weight registers -- loaded once, used for every sentence -- and the same tagged 8-byte exchange {value, tag = step + 1} in two parity buffers,
+// now per sentence: sentence s owns the entries [s * BV_END, (s + 1) * BV_END).  What changes is the ORDER of a step: layer L runs for all live
+// sentences (stage every sentence's inputs with the polls of all sentences in flight together, compute, publish), then layer L + 1 -- ten hops
+// per step, not ten per sentence -- and the row work of a layer is written as SMAX independent instruction streams (dot products and
+// `wave_total` butterflies of all sentences first, the pointwise math after), so that one sentence's dependent latencies are filled by the others'.
+// SMAX is a compile-time bound (instantiations 2, 4, 8; n_sent <= SMAX at run time): the row work of the slots past n_sent, and of sentences that
+// have ended, is still executed (on stale LDS, results dropped) -- predicating it would split the streams again.
+//
+// Arithmetic: every formula and every summation order is that of wrnn_taco_resident_kernel (the helpers are shared, wrnn_taco.h), so a
+// sentence's mel, attention and step count are BIT-IDENTICAL to decoding it alone with variant 2 (tests/test_gpu_taco_batch.py).  The pointwise
+// lines the compiler contracts in the single kernel (GRU: n = tanh(gi + r gh), h' = (h - n) z + n; LSTM: c' = f c + i g) are written with explicit
+// fmaf in the form the single kernel's ISA has -- c' = fma(f, c, i * g) -- because the default contraction depends on the inlining context.
+// Everything else is compiled with contraction OFF: the residual x + h of the LSTM layers is a multiply and an add in the single kernel (h is
+// published too) and was fused to x + sigm(o) * tanh(c) here by default -- 2.6e-9 on the mel, found by the bitwise test.
+//
+// Ends: sentence s is live until its own stop test (:411, on the polled mel block, as in the single kernel) fires or it reaches max_steps[s].
+// Every workgroup derives the live mask from the same polled words by the same code (nothing about it is exchanged); a sentence that is not
+// live is never polled or published again and its outputs are not touched.  The kernel returns when no sentence is live.
+// WAR safety of the parity buffers is the single kernel's argument per sentence: while s is live every wave publishes an LSTM unit of s in
+// every step.  (tests/test_taco_batch_exchange_model.py checks the protocol, the ends included, under adversarial timing.)
+// Spins: a poll waits at most for the slowest workgroup's layer of eight sentences (tens of microseconds); SPIN_LIMIT iterations of a sleep
+// and up to eight reloads are seconds.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../include/wavernn_amd.h"
+#include "wrnn_device.h"
+#include "wrnn_taco.h"
+
+// (the spin loop's reload over the sentences is unrolled by a later pass than the one `#pragma unroll` asks -- 0 scratch, no indexed registers --
+// and the earlier pass says so in every instantiation)
+#pragma clang diagnostic ignored "-Wpass-failed"
+
+void taco_err(const char *fmt, ...);                                  // wrnn_taco.hip: the message behind wrnn_taco_last_error()
+
+namespace wrnn {
+
+constexpr int B_SMAX = WRNN_TACO_BATCH_MAX, B_NMAX = WRNN_TACO_BATCH_NMAX;
+static_assert(B_NMAX == NT, "one encoder position per thread in the normalisation, one per wave (gw < 256) in the score layer");
+// tagged vectors of ONE sentence: offsets in 8-byte entries, [2 parity buffers][length]
+constexpr int BL_MEL = T_NM * R_MAXR;
+constexpr int BV_MEL = 0, BV_PRE1 = BV_MEL + 2 * BL_MEL, BV_PRE2 = BV_PRE1 + 2 * T_P1, BV_ATTNH = BV_PRE2 + 2 * T_P2, BV_CTX = BV_ATTNH + 2 * T_DD,
+              BV_PQ = BV_CTX + 2 * T_DD, BV_S = BV_PQ + 2 * T_DD, BV_X = BV_S + 2 * B_NMAX, BV_X2 = BV_X + 2 * T_LD, BV_X3 = BV_X2 + 2 * T_LD,
+              BV_H1 = BV_X3 + 2 * T_LD, BV_H2 = BV_H1 + 2 * T_LD, BV_END = BV_H2 + 2 * T_LD;
+
+struct TacoBatchSent {
+    const float *seq, *seq_proj;          // [n][256]
+    float *mel_out, *scores_out;          // [max_steps][80][r], [max_steps][n]
+    int n, max_steps;                     // (0, 0 in the slots past n_sent)
+};
+struct TacoBatchArgs {
+    wrnn_taco_weights w;
+    TacoBatchSent s[B_SMAX];              // the per-sentence table travels by value
+    unsigned *uw;                         // the status words' block (as wrnn_taco_decode lays it out)
+    unsigned long long *tv;               // tagged vectors [n_sent][BV_END]
+    int *steps_done;                      // [n_sent]
+    int n_sent, r, max_r;
+    float stop_threshold;
+};
+
+// a value that is the same in every lane, moved to a scalar register
+__device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+
+// No contraction of this kernel's own expressions: where the single kernel's ISA has a fused multiply-add the source below says fmaf, and where
+// it has a multiply and an add (x + h of the residual LSTMs: h is published too) the two stay apart.  Left to the default, the compiler fuses
+// x + sigm(o) * tanh(c) here and not there.
+#pragma clang fp contract(off)
+
+template <int SMAX>
+__global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float xb[SMAX][2][1024];  // a layer's input vector(s); layers alternate the two buffers
+    __shared__ __attribute__((aligned(16))) float melv[SMAX][BL_MEL]; // the previous step's mel block (stop test + prenet input)
+    __shared__ __attribute__((aligned(16))) float ahv[SMAX][T_DD];    // attn_h of this step (query layer and rnn_input)
+    __shared__ __attribute__((aligned(16))) float sc[SMAX][B_NMAX];   // scores of the step (raw, then normalised)
+    __shared__ __attribute__((aligned(16))) float att[SMAX][B_NMAX];  // this workgroup's copy of the previous attention ...
+    __shared__ __attribute__((aligned(16))) float cum[SMAX][B_NMAX];  // ... and of the cumulative attention (:205-206)
+    __shared__ __attribute__((aligned(16))) float convT[2 * T_AK * T_AF];   // location conv weights, [tap of (channel, k)][filter]
+    __shared__ __attribute__((aligned(16))) float LT[T_AF * T_DD];          // L weights, [filter][dim]
+    __shared__ float red[SMAX][NW];
+    __shared__ unsigned nbw[NW];
+    __shared__ int misc[4];
+    // (The score layer's per-wave window (62 floats) lives in xb[s][0][256 + 64 w ...) and its filter outputs (32) in xb[s][1][384 + 32 w ...): both
+    // ranges are free at that point of a step and are re-staged before they are read again.  NOT xb[s][.][512 ...): the recurrent halves of the
+    // GRU / LSTM inputs are not polled at step 0 and must still hold the zeros of the initial state.)
+
+    const int tid = threadIdx.x, lane = tid & 63, wg = blockIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);           // (scalar: the wave's rows, biases and cell states stay out of the vector registers)
+    const int gw = wg * NW + w;
+    const int gt = wg * NT + tid, NGT = R_NWG * NT;
+    const int r = a.r, nmel = T_NM * a.r;
+    const __amdgpu_buffer_rsrc_t vrs = make_rsrc(a.tv, (unsigned)a.n_sent * (unsigned)(BV_END * 8));
+    unsigned *status = a.uw + U_STATUS;
+    bool ok = true;
+
+    // ---------------- resident weights (float4 chunk c of a row: k = 4 lane + 256 c), as in wrnn_taco_resident_kernel ----------------
+    const int k0 = 4 * lane;
+    // LEAN (the 8-sentence form): the rows used once per step by a single butterfly -- prenet, query, mel, the second chunk of the GRU's input
+    // rows, v and the L bias -- are NOT resident: they are re-read every step (1 KB per wave and row, contiguous, from L2, in flight under the
+    // layer's poll), because 200 weight registers and eight sentences' state do not fit 512 registers without scratch.  The values are the same.
+    constexpr bool LEAN = SMAX > 4;
+    const bool u256 = gw < T_DD, u128 = gw < T_P2;
+#define LD_FC1() ldw4(a.w.prenet_fc1_w + (size_t)gw * T_NM + k0, u256 && k0 < T_NM)
+#define LD_FC2() ldw4(a.w.prenet_fc2_w + (size_t)gw * T_P1 + k0, u128)
+#define LD_GI1(q) ldw4(a.w.attn_rnn_w_ih + (size_t)((q) * T_DD + gw) * (T_DD + T_P2) + 256 + k0, u256 && k0 < T_P2)
+#define LD_Q() ldw4(a.w.attn_W_w + (size_t)gw * T_DD + k0, u256)
+#define LD_MP(c) ldw4(a.w.mel_proj_w + (size_t)((gw / r) * a.max_r + gw % r) * T_LD + 256 * (c) + k0, gw < nmel)
+#define LD_V() ldw4(a.w.attn_v_w + k0, true)
+#define LD_LB() ldw4(a.w.attn_L_b + k0, true)
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 w_fc1 = LEAN ? z4 : LD_FC1();
+    const float4 w_fc2 = LEAN ? z4 : LD_FC2();
+    float4 g_i[3][2], g_h[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const size_t row = (size_t)(q * T_DD + gw);
+        g_i[q][0] = ldw4(a.w.attn_rnn_w_ih + row * (T_DD + T_P2) + k0, u256);
+        g_i[q][1] = LEAN ? z4 : LD_GI1(q);
+        g_h[q] = ldw4(a.w.attn_rnn_w_hh + row * T_DD + k0, u256);
+    }
+    const float4 w_q = LEAN ? z4 : LD_Q();
+    float4 w_ri[2], l1i[4][2], l1h[4][2], l2i[4][2], l2h[4][2], w_mp[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        w_ri[c] = ldw4(a.w.rnn_input_w + (size_t)gw * (2 * T_DD) + 256 * c + k0, true);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t row = (size_t)(q * T_LD + gw) * T_LD + 256 * c + k0;
+            l1i[q][c] = ldw4(a.w.rnn1_w_ih + row, true); l1h[q][c] = ldw4(a.w.rnn1_w_hh + row, true);
+            l2i[q][c] = ldw4(a.w.rnn2_w_ih + row, true); l2h[q][c] = ldw4(a.w.rnn2_w_hh + row, true);
+        }
+        w_mp[c] = LEAN ? z4 : LD_MP(c);
+    }
+    const float4 v_w0 = LEAN ? z4 : LD_V(), L_b0 = LEAN ? z4 : LD_LB();
+    // biases of this wave's rows (wave-uniform)
+    const float b_fc1 = u256 ? a.w.prenet_fc1_b[gw] : 0.f, b_fc2 = u128 ? a.w.prenet_fc2_b[gw] : 0.f;
+    const float b_q = u256 ? a.w.attn_W_b[gw] : 0.f;
+    float b_gi[3], b_gh[3], b_l1[4], b_l1h[4], b_l2[4], b_l2h[4];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { b_gi[q] = u256 ? a.w.attn_rnn_b_ih[q * T_DD + gw] : 0.f; b_gh[q] = u256 ? a.w.attn_rnn_b_hh[q * T_DD + gw] : 0.f; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        b_l1[q] = a.w.rnn1_b_ih[q * T_LD + gw]; b_l1h[q] = a.w.rnn1_b_hh[q * T_LD + gw];
+        b_l2[q] = a.w.rnn2_b_ih[q * T_LD + gw]; b_l2h[q] = a.w.rnn2_b_hh[q * T_LD + gw];
+    }
+    const float b_ri = a.w.rnn_input_b[gw];
+
+    // ---------------- per sentence: context columns (n <= 256: four positions per lane) and cell states.  (The projection row of position gw,
+    // one float4 per lane and sentence, is re-read every step -- 1 KB per wave, contiguous, in flight under the poll of the query: eight of
+    // them resident are what the register file of the 8-sentence form no longer holds.) ----
+    int ns[SMAX];
+    float seqc[SMAX][4];                                               // context dim gw: encoder_seq[pos = lane + 64 i][gw]
+    float c1[SMAX], c2[SMAX];                                          // this wave's LSTM cell states (uniform over the lanes: kept in scalar registers)
+    int dn[SMAX];                                                      // steps run (set when the sentence ends)
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+        ns[s] = s < a.n_sent ? a.s[s].n : 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) seqc[s][i] = (u256 && lane + 64 * i < ns[s]) ? a.s[s].seq[(size_t)(lane + 64 * i) * T_DD + gw] : 0.f;
+        c1[s] = 0.f; c2[s] = 0.f; dn[s] = 0;
+    }
+
+    // ---------------- LDS: attention weights (transposed: conflict-free lane strides), zero state ----------------
+    for (int k = tid; k < T_AF * 2 * T_AK; k += NT) convT[(k % (2 * T_AK)) * T_AF + k / (2 * T_AK)] = a.w.attn_conv_w[k];
+    for (int k = tid; k < T_DD * T_AF; k += NT) LT[(k % T_AF) * T_DD + k / T_AF] = a.w.attn_L_w[k];
+    for (int k = tid; k < SMAX * 2 * 1024; k += NT) (&xb[0][0][0])[k] = 0.f;
+    for (int k = tid; k < SMAX * BL_MEL; k += NT) (&melv[0][0])[k] = 0.f;
+    for (int k = tid; k < SMAX * B_NMAX; k += NT) { (&sc[0][0])[k] = 0.f; (&att[0][0])[k] = 0.f; (&cum[0][0])[k] = 0.f; (&ahv[0][0])[k] = 0.f; }
+    if (tid < 4) misc[tid] = 0;
+    __syncthreads();
+
+    // the layers with several butterflies per sentence (GRU, scores, LSTMs) run in groups of G sentences: enough independent streams to fill the
+    // pipeline, and the group's operands fit the register file (the pointwise math between two groups keeps the scheduler from merging them)
+    constexpr int G = SMAX < 4 ? SMAX : 4;
+    unsigned live = (1u << a.n_sent) - 1u;                             // bit s: sentence s is still decoding (wave-uniform, the same in every workgroup)
+#define LV(s) ((live >> (s)) & 1u)
+
+    // entries [ventry, ventry + cnt(s)) of every live sentence s -> dst + s * dstride, each polled until it carries `tag`; the loads of all
+    // sentences are in flight together
+    auto poll_in = [&](float *dst, int dstride, int ventry, int cntmax, auto cnt, unsigned tag, unsigned code) {
+        for (int q0 = 0; q0 < cntmax; q0 += NT) {
+            const int q = q0 + tid;
+            u32x2 e[SMAX];
+            bool in[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                in[s] = LV(s) && q < cnt(s);
+                e[s] = u32x2{0u, tag};
+                if (in[s]) e[s] = __builtin_amdgcn_raw_buffer_load_b64(vrs, (s * BV_END + ventry + q) * 8, 0, 16 /* sc1 */);
+            }
+            unsigned spins = 0;
+            for (;;) {
+                bool pend = false;
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s) pend = pend || e[s].y != tag;
+                if (!__any(pend)) break;
+                if ((++spins & 255u) == 0u && (spins > SPIN_LIMIT || ld_agent32(status) != 0u)) {
+                    if (lane == 0) report_failure(status, 0x900u | code, wg, tag, tid);
+                    ok = false;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s)
+                    if (e[s].y != tag) e[s] = __builtin_amdgcn_raw_buffer_load_b64(vrs, (s * BV_END + ventry + q) * 8, 0, 16 /* sc1 */);
+            }
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (in[s]) dst[s * dstride + q] = __uint_as_float(e[s].x);
+        }
+    };
+    auto pub = [&](int s, int ventry, float v, unsigned tag) {
+        if (lane == 0) {
+            const u32x2 e = {__float_as_uint(v), tag};
+            __builtin_amdgcn_raw_buffer_store_b64(e, vrs, (s * BV_END + ventry) * 8, 0, 16 /* sc1 */);
+        }
+    };
+#define FIXED(c) [&](int) { return (c); }
+#define STAGED()                            \
+    do {                                    \
+        if (!ok) misc[0] = 1;               \
+        __syncthreads();                    \
+        if (misc[0] != 0) return;           \
+    } while (0)
+
+    for (int step = 0;; ++step) {
+        const int p = step & 1;
+        const unsigned tag = (unsigned)step + 1u, ptag = (unsigned)step;      // this step's entries / the previous step's
+        // ---- ends by limit; the previous step's mel blocks: stop test of :411 per sentence ----------------------------------
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s)
+            if (LV(s) && step >= a.s[s].max_steps) { live &= ~(1u << s); dn[s] = step; }
+        if (live == 0u) break;
+        const float4 wfc1 = LEAN ? LD_FC1() : w_fc1;
+        if (step > 0) poll_in(&melv[0][0], BL_MEL, BV_MEL + (p ^ 1) * BL_MEL, nmel, FIXED(nmel), ptag, 1);
+        STAGED();
+        {
+            unsigned nb = 0u;
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                int notbelow = 0;
+                for (int q = tid; q < nmel; q += NT) notbelow |= !(melv[s][q] < a.stop_threshold);
+                if (__any(notbelow)) nb |= 1u << s;
+            }
+            if (lane == 0) nbw[w] = nb;
+            __syncthreads();
+            const unsigned any = (unsigned)__builtin_amdgcn_readfirstlane((int)((nbw[0] | nbw[1]) | (nbw[2] | nbw[3])));
+            if (step > 0 && (step - 1) * r > 10) {                     // `(mel_frames < stop_threshold).all() and t > 10`, t = (step - 1) r
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s)
+                    if (LV(s) && !((any >> s) & 1u)) { live &= ~(1u << s); dn[s] = step; }
+            }
+            if (live == 0u) break;
+        }
+        // ---- L1: PreNet fc1 on the last column of the previous block (<GO> = zeros) ----
+        if (u256) {
+            float t1[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                float x = 0.f;
+                if (k0 < T_NM) {                                       // the last frame of the block: column j = r - 1 of rows m = k0 .. k0 + 3
+                    x = fmaf(wfc1.x, melv[s][k0 * r + r - 1], x);
+                    x = fmaf(wfc1.y, melv[s][(k0 + 1) * r + r - 1], x);
+                    x = fmaf(wfc1.z, melv[s][(k0 + 2) * r + r - 1], x);
+                    x = fmaf(wfc1.w, melv[s][(k0 + 3) * r + r - 1], x);
+                }
+                t1[s] = wave_total(x);
+            }
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s)) pub(s, BV_PRE1 + p * T_P1 + gw, fmaxf(t1[s] + b_fc1, 0.f), tag);
+        }
+        // ---- L2: PreNet fc2 ----
+        const float4 wfc2 = LEAN ? LD_FC2() : w_fc2;
+        poll_in(&xb[0][0][0], 2048, BV_PRE1 + p * T_P1, T_P1, FIXED(T_P1), tag, 2);
+        STAGED();
+        if (u128) {
+            float t2[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) t2[s] = wave_total(fma4(wfc2, xb[s][0] + k0, 0.f));
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s)) pub(s, BV_PRE2 + p * T_P2 + gw, fmaxf(t2[s] + b_fc2, 0.f), tag);
+        }
+        // ---- L3: attention GRUCell on [context(t-1), prenet] with h = attn_h(t-1) (:233-235) ----
+        float4 gi1[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) gi1[q] = LEAN ? LD_GI1(q) : g_i[q][1];
+        if (step > 0) {
+            poll_in(&xb[0][1][0], 2048, BV_CTX + (p ^ 1) * T_DD, T_DD, FIXED(T_DD), ptag, 3);
+            poll_in(&xb[0][1][512], 2048, BV_ATTNH + (p ^ 1) * T_DD, T_DD, FIXED(T_DD), ptag, 3);
+        }
+        poll_in(&xb[0][1][T_DD], 2048, BV_PRE2 + p * T_P2, T_P2, FIXED(T_P2), tag, 3);
+        STAGED();
+        if (u256) {
+#pragma unroll
+          for (int s0 = 0; s0 < SMAX; s0 += G) {
+            float gi[SMAX][3], gh[SMAX][3];
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    float x = fma4(g_i[q][0], xb[s][1] + k0, 0.f);
+                    if (k0 < T_P2) x = fma4(gi1[q], xb[s][1] + 256 + k0, x);
+                    gi[s][q] = wave_total(x) + b_gi[q];
+                    gh[s][q] = wave_total(fma4(g_h[q], xb[s][1] + 512 + k0, 0.f)) + b_gh[q];
+                }
+            }
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+                const float rg = sigm(gi[s][0] + gh[s][0]), zg = sigm(gi[s][1] + gh[s][1]);
+                const float ng = tanhf(fmaf(rg, gh[s][2], gi[s][2]));
+                const float h = xb[s][1][512 + gw];
+                if (LV(s)) pub(s, BV_ATTNH + p * T_DD + gw, fmaf(h - ng, zg, ng), tag);
+            }
+          }
+        }
+        // ---- L4: processed query (:193) ----
+        const float4 wq = LEAN ? LD_Q() : w_q;
+        poll_in(&ahv[0][0], T_DD, BV_ATTNH + p * T_DD, T_DD, FIXED(T_DD), tag, 4);
+        STAGED();
+        if (u256) {
+            float t4[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) t4[s] = wave_total(fma4(wq, ahv[s] + k0, 0.f));
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s)) pub(s, BV_PQ + p * T_DD + gw, t4[s] + b_q, tag);
+        }
+        // ---- L5: location-sensitive scores (:194-203): wave gw is encoder position gw of every sentence ----
+        const float4 v_w = LEAN ? LD_V() : v_w0, L_b = LEAN ? LD_LB() : L_b0;
+        float4 spj[SMAX];                                              // encoder_seq_proj row of the position gw
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s) spj[s] = ldw4(a.s[s].seq_proj + (size_t)gw * T_DD + k0, LV(s) && gw < ns[s]);
+        poll_in(&xb[0][1][0], 2048, BV_PQ + p * T_DD, T_DD, FIXED(T_DD), tag, 5);
+        STAGED();
+        if (u256) {
+            const int pos = gw;
+#pragma unroll
+          for (int s0 = 0; s0 < SMAX; s0 += G) {
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+                float *win = &xb[s][0][256 + 64 * w];
+                if (lane < 2 * T_AK) {
+                    const int c = lane / T_AK, k = lane % T_AK, idx = pos + k - T_AK / 2;
+                    win[lane] = (idx >= 0 && idx < ns[s]) ? (c == 0 ? cum[s][idx] : att[s][idx]) : 0.f;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane < T_AF) {
+#pragma unroll
+                for (int s = s0; s < s0 + G; ++s) {
+                    const float *win = &xb[s][0][256 + 64 * w];
+                    float x = 0.f;
+                    for (int q = 0; q < 2 * T_AK; ++q) x = fmaf(convT[q * T_AF + lane], win[q], x);
+                    xb[s][1][384 + T_AF * w + lane] = x;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            float t5[SMAX];
+            float pl[G][4];
+#pragma unroll
+            for (int j = 0; j < G; ++j) { pl[j][0] = L_b.x; pl[j][1] = L_b.y; pl[j][2] = L_b.z; pl[j][3] = L_b.w; }
+#pragma unroll 8
+            for (int f = 0; f < T_AF; ++f) {                            // (one read of the L row per filter for the whole group; per sentence the
+                const float4 lw = *reinterpret_cast<const float4 *>(LT + f * T_DD + k0);      //  sum runs over f in the single kernel's order)
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    const float cv = xb[s0 + j][1][384 + T_AF * w + f];
+                    pl[j][0] = fmaf(lw.x, cv, pl[j][0]); pl[j][1] = fmaf(lw.y, cv, pl[j][1]);
+                    pl[j][2] = fmaf(lw.z, cv, pl[j][2]); pl[j][3] = fmaf(lw.w, cv, pl[j][3]);
+                }
+            }
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+                const float4 xq = *reinterpret_cast<const float4 *>(xb[s][1] + k0);
+                const float4 sp = spj[s];
+                float u = 0.f;
+                u = fmaf(v_w.x, tanhf(xq.x + sp.x + pl[s - s0][0]), u);
+                u = fmaf(v_w.y, tanhf(xq.y + sp.y + pl[s - s0][1]), u);
+                u = fmaf(v_w.z, tanhf(xq.z + sp.z + pl[s - s0][2]), u);
+                u = fmaf(v_w.w, tanhf(xq.w + sp.w + pl[s - s0][3]), u);
+                t5[s] = wave_total(u);
+            }
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s)
+                if (LV(s) && pos < ns[s]) pub(s, BV_S + p * B_NMAX + pos, sigm(t5[s]), tag);
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+        // ---- L6: normalise (:204), this workgroup's copies of attention / cumulative (:205-206), context (:207) ----
+        poll_in(&sc[0][0], B_NMAX, BV_S + p * B_NMAX, B_NMAX, [&](int s) { return ns[s]; }, tag, 6);
+        STAGED();
+        {
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                float part = 0.f;
+                if (tid < ns[s]) part += sc[s][tid];
+                part = wave_total(part);                               // the same tree in every workgroup: the same total everywhere
+                if (lane == 0) red[s][w] = part;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                const float total = (red[s][0] + red[s][1]) + (red[s][2] + red[s][3]);
+                if (LV(s) && tid < ns[s]) {
+                    const float v = sc[s][tid] / total;
+                    sc[s][tid] = v; att[s][tid] = v; cum[s][tid] += v;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s))
+                    for (int pos = gt; pos < ns[s]; pos += NGT) a.s[s].scores_out[(size_t)step * ns[s] + pos] = sc[s][pos];
+            if (u256) {
+                float t6[SMAX];
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s) {
+                    float x = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (64 * i < ns[s]) x = fmaf(sc[s][lane + 64 * i], seqc[s][i], x);
+                    t6[s] = wave_total(x);
+                }
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s)
+                    if (LV(s)) pub(s, BV_CTX + p * T_DD + gw, t6[s], tag);
+            }
+        }
+        // ---- L7: rnn_input on [context, attn_h] (:246-247) ----
+        poll_in(&xb[0][0][0], 2048, BV_CTX + p * T_DD, T_DD, FIXED(T_DD), tag, 7);
+        STAGED();
+        {
+            float t7[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) t7[s] = wave_total(fma4(w_ri[1], ahv[s] + k0, fma4(w_ri[0], xb[s][0] + k0, 0.f)));
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s)) pub(s, BV_X + p * T_LD + gw, t7[s] + b_ri, tag);
+        }
+        // ---- L8: residual LSTMCell 1 (:249-251; ATen lstm_cell: gates i, f, g, o) ----
+        poll_in(&xb[0][1][0], 2048, BV_X + p * T_LD, T_LD, FIXED(T_LD), tag, 8);
+        if (step > 0) poll_in(&xb[0][1][T_LD], 2048, BV_H1 + (p ^ 1) * T_LD, T_LD, FIXED(T_LD), ptag, 8);
+        STAGED();
+#pragma unroll
+        for (int s0 = 0; s0 < SMAX; s0 += G) {
+            float g4[SMAX][4];
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    g4[s][q] = wave_total(fma4(l1i[q][1], xb[s][1] + 256 + k0, fma4(l1i[q][0], xb[s][1] + k0, 0.f))) + b_l1[q] +
+                               wave_total(fma4(l1h[q][1], xb[s][1] + T_LD + 256 + k0, fma4(l1h[q][0], xb[s][1] + T_LD + k0, 0.f))) + b_l1h[q];
+            }
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+                c1[s] = uni(fmaf(sigm(g4[s][1]), c1[s], sigm(g4[s][0]) * tanhf(g4[s][2])));
+                const float h = sigm(g4[s][3]) * tanhf(c1[s]);
+                if (LV(s)) {
+                    pub(s, BV_H1 + p * T_LD + gw, h, tag);
+                    pub(s, BV_X2 + p * T_LD + gw, xb[s][1][gw] + h, tag);
+                }
+            }
+        }
+        // ---- L9: residual LSTMCell 2 (:254-256) ----
+        poll_in(&xb[0][0][0], 2048, BV_X2 + p * T_LD, T_LD, FIXED(T_LD), tag, 9);
+        if (step > 0) poll_in(&xb[0][0][T_LD], 2048, BV_H2 + (p ^ 1) * T_LD, T_LD, FIXED(T_LD), ptag, 9);
+        STAGED();
+#pragma unroll
+        for (int s0 = 0; s0 < SMAX; s0 += G) {
+            float g4[SMAX][4];
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    g4[s][q] = wave_total(fma4(l2i[q][1], xb[s][0] + 256 + k0, fma4(l2i[q][0], xb[s][0] + k0, 0.f))) + b_l2[q] +
+                               wave_total(fma4(l2h[q][1], xb[s][0] + T_LD + 256 + k0, fma4(l2h[q][0], xb[s][0] + T_LD + k0, 0.f))) + b_l2h[q];
+            }
+#pragma unroll
+            for (int s = s0; s < s0 + G; ++s) {
+                c2[s] = uni(fmaf(sigm(g4[s][1]), c2[s], sigm(g4[s][0]) * tanhf(g4[s][2])));
+                const float h = sigm(g4[s][3]) * tanhf(c2[s]);
+                if (LV(s)) {
+                    pub(s, BV_H2 + p * T_LD + gw, h, tag);
+                    pub(s, BV_X3 + p * T_LD + gw, xb[s][0][gw] + h, tag);
+                }
+            }
+        }
+        // ---- L10: mel_proj (:262-263): entry q = m r + j is row (m, j) of the (n_mels, max_r) view ----
+        const float4 wmp0 = LEAN ? LD_MP(0) : w_mp[0], wmp1 = LEAN ? LD_MP(1) : w_mp[1];
+        poll_in(&xb[0][1][0], 2048, BV_X3 + p * T_LD, T_LD, FIXED(T_LD), tag, 10);
+        STAGED();
+        if (gw < nmel) {
+            float t10[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) t10[s] = wave_total(fma4(wmp1, xb[s][1] + 256 + k0, fma4(wmp0, xb[s][1] + k0, 0.f)));
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s)) {
+                    if (lane == 0) a.s[s].mel_out[(size_t)step * nmel + gw] = t10[s];
+                    pub(s, BV_MEL + p * BL_MEL + gw, t10[s], tag);
+                }
+        }
+        for (int q = gw + R_NWV; q < nmel; q += R_NWV) {              // r >= 7 only: the rows past the 512 resident ones, from L2
+            const float *wr = a.w.mel_proj_w + (size_t)((q / r) * a.max_r + q % r) * T_LD;
+            const float4 wa = ldw4(wr + k0, true), wb = ldw4(wr + 256 + k0, true);
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) {
+                const float x = wave_total(fma4(wb, xb[s][1] + 256 + k0, fma4(wa, xb[s][1] + k0, 0.f)));
+                if (LV(s)) {
+                    if (lane == 0) a.s[s].mel_out[(size_t)step * nmel + q] = x;
+                    pub(s, BV_MEL + p * BL_MEL + q, x, tag);
+                }
+            }
+        }
+    }
+    if (gt == 0) {
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s)
+            if (s < a.n_sent) a.steps_done[s] = dn[s];
+    }
+#undef STAGED
+#undef FIXED
+#undef LV
+#undef LD_FC1
+#undef LD_FC2
+#undef LD_GI1
+#undef LD_Q
+#undef LD_MP
+#undef LD_V
+#undef LD_LB
+}
+
+}  // namespace wrnn
+
+using namespace wrnn;
+
+// workspace: the single-sentence decoder's prefix ([A_END floats | U_END words]: the status words stay where wrnn_taco_status reads them), then
+// the tagged vectors of n_sent sentences
+constexpr size_t TACO_PREFIX_BYTES = (size_t)A_END * 4 + (size_t)U_END * 4;
+static_assert(TACO_PREFIX_BYTES % 8 == 0, "tagged entries are 8-byte aligned");
+
+extern "C" size_t wrnn_taco_batch_workspace_bytes(int32_t n_sent)
+{
+    if (n_sent < 1 || n_sent > B_SMAX) return 0;
+    return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8;
+}
+
+extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
+{
+    // ---- arguments: everything is checked before the first HIP call ----
+    if (!w || !c) { taco_err("null argument"); return WRNN_ERR_ARG; }
+    if (c->struct_bytes != sizeof(wrnn_taco_batch_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
+        taco_err("struct size mismatch (header / library versions differ)");
+        return WRNN_ERR_ARG;
+    }
+    if (c->n_sent < 1 || c->n_sent > B_SMAX) {
+        taco_err("n_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", c->n_sent, B_SMAX);
+        return WRNN_ERR_ARG;
+    }
+    if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
+        taco_err("r=%d max_r=%d: frames per step must be 1..min(max_r, %d)", c->r, c->max_r, R_MAXR);
+        return WRNN_ERR_ARG;
+    }
+    if (!c->n || !c->max_steps || !c->seq || !c->seq_proj || !c->mel_out || !c->scores_out || !c->steps_done || !c->workspace) {
+        taco_err("null buffer: n, max_steps, seq, seq_proj, mel_out, scores_out, steps_done and workspace are all required");
+        return WRNN_ERR_ARG;
+    }
+    for (int s = 0; s < c->n_sent; ++s) {
+        if (c->n[s] < 1 || c->n[s] > B_NMAX) {
+            taco_err("sentence %d: n=%d encoder positions, the batched kernel takes 1..%d (WRNN_TACO_BATCH_NMAX; longer: wrnn_taco_decode)", s, c->n[s], B_NMAX);
+            return WRNN_ERR_ARG;
+        }
+        if (c->max_steps[s] < 1) {
+            taco_err("sentence %d: max_steps=%d, at least 1", s, c->max_steps[s]);
+            return WRNN_ERR_ARG;
+        }
+        if (!c->seq[s] || !c->seq_proj[s] || !c->mel_out[s] || !c->scores_out[s]) {
+            taco_err("sentence %d: null buffer (seq, seq_proj, mel_out and scores_out are required)", s);
+            return WRNN_ERR_ARG;
+        }
+    }
+    if (c->workspace_bytes < wrnn_taco_batch_workspace_bytes(c->n_sent)) {
+        taco_err("workspace of %zu bytes, %d sentences need %zu (wrnn_taco_batch_workspace_bytes)", c->workspace_bytes, c->n_sent,
+                 wrnn_taco_batch_workspace_bytes(c->n_sent));
+        return WRNN_ERR_ARG;
+    }
+    if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
+        w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
+        taco_err("unsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)");
+        return WRNN_ERR_ARG;
+    }
+    // ---- device ----
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if (prop.multiProcessorCount < R_NWG) {
+        taco_err("the batched decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
+                 prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
+    TacoBatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.w = *w;
+    for (int s = 0; s < c->n_sent; ++s) {
+        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
+        a.s[s].n = c->n[s]; a.s[s].max_steps = c->max_steps[s];
+    }
+    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
+    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
+    a.steps_done = c->steps_done;
+    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
+    a.stop_threshold = c->stop_threshold;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
+    if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    void *params[] = {(void *)&a};
+    const void *kern = c->n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2> : c->n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4>
+                                                                                                   : (const void *)wrnn_taco_batch_kernel<8>;
+    e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
+    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
+    return WRNN_OK;
+}

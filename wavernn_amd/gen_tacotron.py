@@ -6,7 +6,11 @@ the postnet / post_proj output, 80 bins because fft_bins = hp.num_mels) -> (m + 
 Flags follow the reference where they exist (--input_text/-i, --tts_weights, --batched/-b, --unbatched/-u, --target/-t,
 --overlap/-o, --voc_weights); hparams.py is replaced by the shipped defaults.  Without --input_text every line of
 --sentences (default: none) is synthesised.  Text cleaning is the basic pipeline (lowercase, whitespace): number and
-abbreviation expansion need the reference's text front-end (out of scope)."""
+abbreviation expansion need the reference's text front-end (out of scope).
+
+`--batch N` (with --batched): all sentences at once -- the Tacotron decoder loops in groups of N <= 8 sentences per persistent kernel
+(`TacotronInference.generate_batch`, csrc/wrnn_taco_batch.hip), then ONE vocoder pass over all of them (`generate_corpus`, noise drawn inside the
+library under the seeds --seed, --seed + 1, ...).  Same file names.  Without the flag the per-sentence path runs as before."""
 import argparse
 import time
 from pathlib import Path
@@ -33,8 +37,14 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=2000, help='decoder step limit (Tacotron.generate default)')
     ap.add_argument('--output', default='.', help='output directory')
     ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet)')
+    ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (needs --batched)')
+    ap.add_argument('--seed', type=int, default=0, help='--batch: sentence i draws its sampling noise under seed + i')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
+    if a.batch is not None and not a.batched:
+        ap.error('--batch needs --batched (the one-pass vocoder folds every sentence)')
+    if a.batch is not None and not 1 <= a.batch <= 8:
+        ap.error('--batch: 1..8 sentences per decoder kernel')
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     voc = WaveRNN(**SHIPPED, mode=a.mode).to('cuda')
@@ -50,13 +60,30 @@ def main(argv=None):
     out_dir.mkdir(parents=True, exist_ok=True)
     v_type = 'wavernn_batched' if a.batched else 'wavernn_unbatched'
     tts_k = int(tts.p['step'].item()) // 1000 if 'step' in tts.p else 0
+    names = [f'__input_{text[:10]}_{v_type}_{tts_k}k.wav' if a.input_text else f'{i}_{v_type}_{tts_k}k.wav' for i, text in enumerate(texts, 1)]
+    if a.batch is not None:
+        from .batch import generate_corpus
+        from .dsp import save_wav
+        print(f'\n| Generating {len(texts)} sentences, {a.batch} per decoder kernel')
+        t0 = time.perf_counter()
+        outs = tts.generate_batch([text_to_ids(t) for t in texts], steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel, max_batch=a.batch)
+        t1 = time.perf_counter()
+        mels = [torch.tensor(tacotron_to_wavernn_mel(lin)).unsqueeze(0) for _, lin, _ in outs]          # the POSTNET output (:142)
+        wavs = generate_corpus(voc, mels, a.target, a.overlap, True, seeds=[a.seed + i for i in range(len(mels))], noise_source='library')
+        t2 = time.perf_counter()
+        for name, wav, (_, lin, _) in zip(names, wavs, outs):
+            save_wav(np.asarray(wav), out_dir / name, voc.sample_rate)
+            print(f'{name}: {lin.shape[1]} frames, {len(wav) / voc.sample_rate:.2f} s of audio')
+        print(f'Tacotron {(t1 - t0) * 1e3:.0f} ms, vocoder {(t2 - t1) * 1e3:.0f} ms for {len(texts)} sentences')
+        print('\n\nDone.\n')
+        return
     for i, text in enumerate(texts, 1):
         print(f'\n| Generating {i}/{len(texts)}')
         t0 = time.perf_counter()
         _, mel, _ = tts.generate(text_to_ids(text), steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel)   # the POSTNET output (:142)
         t1 = time.perf_counter()
         m = torch.tensor(tacotron_to_wavernn_mel(mel)).unsqueeze(0)
-        name = f'__input_{text[:10]}_{v_type}_{tts_k}k.wav' if a.input_text else f'{i}_{v_type}_{tts_k}k.wav'
+        name = names[i - 1]
         wav = voc.generate(m, out_dir / name, a.batched, a.target, a.overlap, True)
         t2 = time.perf_counter()
         print(f'{name}: {mel.shape[1]} frames, {wav.shape[0] / voc.sample_rate:.2f} s of audio; Tacotron {(t1 - t0) * 1e3:.0f} ms, '

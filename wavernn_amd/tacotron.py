@@ -11,6 +11,7 @@ persistent kernel (`generate(..., kernel=True)`: `wrnn_taco_decode`, csrc/wrnn_t
 bidirectional GRUs as `wrnn_bigru`; the eager loop stays as the any-device form.  `generate(..., cbhg_kernel=True)` (opt-in) also runs
 the encoder and the post-net -- embedding, pre-net, both CBHGs, `encoder_proj`, `post_proj` -- as HIP kernels through the C ABI
 (`wrnn_taco_encode` / `wrnn_taco_postnet`, csrc/wrnn_cbhg.hip), so that the whole Tacotron side is behind include/wavernn_amd.h.
+`generate_batch(list_of_ids)` decodes up to eight sentences per pass of the decoder kernel (`wrnn_taco_decode_batch`, csrc/wrnn_taco_batch.hip).
 
     tts = TacotronInference(state_dict, device='cuda')
     _, m, attn = tts.generate(ids, steps=800)                 # same returns as the reference: (80, N), (fft, N), (N, chars); the
@@ -55,6 +56,8 @@ class TacotronInference:
         self.last_front_path = None                # 'hip' / 'torch': what the last generate() ran the encoder and the post-net on
         self._front = None                         # wrnn_taco_front handle (one per instance), False: create refused the dims
         self._front_ws = None                      # its workspace, reused and grown
+        self._dec_w = None                         # generate_batch: (wrnn_taco_weights, the tensors it points to), built once
+        self._batch_ws = None                      # ... and the workspace of wrnn_taco_decode_batch, reused and grown
 
     def _count(self, pattern):
         n = 0
@@ -357,6 +360,109 @@ class TacotronInference:
         k = int(done.item())
         mel = mel_out[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * self.r)      # frames of step s at columns [s r, (s+1) r)
         return mel, scores[:k]
+
+    _DEC_NAMES = dict(prenet_fc1_w='prenet.fc1.weight', prenet_fc1_b='prenet.fc1.bias', prenet_fc2_w='prenet.fc2.weight',
+                      prenet_fc2_b='prenet.fc2.bias', attn_rnn_w_ih='attn_rnn.weight_ih', attn_rnn_w_hh='attn_rnn.weight_hh',
+                      attn_rnn_b_ih='attn_rnn.bias_ih', attn_rnn_b_hh='attn_rnn.bias_hh', attn_W_w='attn_net.W.weight',
+                      attn_W_b='attn_net.W.bias', attn_conv_w='attn_net.conv.weight', attn_L_w='attn_net.L.weight',
+                      attn_L_b='attn_net.L.bias', attn_v_w='attn_net.v.weight', rnn_input_w='rnn_input.weight',
+                      rnn_input_b='rnn_input.bias', rnn1_w_ih='res_rnn1.weight_ih', rnn1_w_hh='res_rnn1.weight_hh',
+                      rnn1_b_ih='res_rnn1.bias_ih', rnn1_b_hh='res_rnn1.bias_hh', rnn2_w_ih='res_rnn2.weight_ih',
+                      rnn2_w_hh='res_rnn2.weight_hh', rnn2_b_ih='res_rnn2.bias_ih', rnn2_b_hh='res_rnn2.bias_hh',
+                      mel_proj_w='mel_proj.weight')
+
+    def decoder_weights(self):
+        """This instance's `wrnn_taco_weights` (the decoder's tensors as float32 device pointers), built on first use and kept: the struct and
+        the tensors it points to live as long as the instance."""
+        import ctypes
+        from . import _lib
+        if self._dec_w is None:
+            keep = {k: self.p['decoder.' + v].detach().to(self.device, torch.float32).contiguous() for k, v in self._DEC_NAMES.items()}
+            w = _lib.TacoWeights()
+            w.struct_bytes = ctypes.sizeof(_lib.TacoWeights)
+            w.n_mels, w.prenet1, w.prenet2 = self.n_mels, keep['prenet_fc1_w'].shape[0], keep['prenet_fc2_w'].shape[0]
+            w.decoder_dims, w.encoder_width, w.lstm_dims = self.decoder_dims, self.p['encoder_proj.weight'].shape[1], self.lstm_dims
+            w.attn_filters, w.attn_kernel = keep['attn_conv_w'].shape[0], keep['attn_conv_w'].shape[2]
+            for k, tns in keep.items():
+                setattr(w, k, tns.data_ptr())
+            self._dec_w = (w, keep)
+        return self._dec_w[0]
+
+    def _decode_batch_kernel(self, encs, steps):
+        """The decoder loops of up to `_lib.TACO_BATCH_MAX` sentences in ONE persistent kernel (`wrnn_taco_decode_batch`,
+        csrc/wrnn_taco_batch.hip).  encs: [(seq (1, n, 256), seq_proj (1, n, 256))], every n <= `_lib.TACO_BATCH_NMAX`.  Returns
+        [(mel (1, n_mels, N_s), attention (N_s / r, n_s))] device tensors, each bit-identical to `_decode_kernel(..., variant=2)`."""
+        import ctypes
+        from . import _lib
+        dev = self.device
+        if dev.type != 'cuda':
+            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
+        L, S = _lib.lib(), len(encs)
+        max_steps = (steps + self.r - 1) // self.r
+        seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
+        projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
+        mels = [torch.zeros(max_steps, self.n_mels, self.r, device=dev) for _ in encs]
+        scores = [torch.zeros(max_steps, q.size(0), device=dev) for q in seqs]
+        done = torch.zeros(S, dtype=torch.int32, device=dev)
+        need = int(L.wrnn_taco_batch_workspace_bytes(S))
+        if self._batch_ws is None or self._batch_ws.numel() < need:
+            self._batch_ws = torch.empty(max(need, int(L.wrnn_taco_batch_workspace_bytes(min(_lib.TACO_BATCH_MAX, max(S, 1))))), dtype=torch.uint8, device=dev)
+        ws = self._batch_ws
+        c = _lib.TacoBatchCall()
+        c.struct_bytes = ctypes.sizeof(_lib.TacoBatchCall)
+        c.n_sent, c.r, c.max_r, c.stop_threshold = S, self.r, self.max_r, self.stop_threshold
+        c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
+        c.max_steps = (ctypes.c_int32 * S)(*([max_steps] * S))
+        for name, ts in (('seq', seqs), ('seq_proj', projs), ('mel_out', mels), ('scores_out', scores)):
+            setattr(c, name, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
+        c.steps_done, c.workspace, c.workspace_bytes = done.data_ptr(), ws.data_ptr(), ws.numel()
+        c.stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = L.wrnn_taco_decode_batch((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(self.decoder_weights()),
+                                      ctypes.byref(c))
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_decode_batch failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        st4 = (ctypes.c_uint32 * 4)()
+        rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
+        if rc != _lib.WRNN_OK or st4[0] != 0:
+            raise _lib.WrnnError(f'Tacotron batched decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
+        ks = [int(k) for k in done.cpu()]
+        return [(m[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * self.r), a[:k]) for m, a, k in zip(mels, scores, ks)]
+
+    @torch.no_grad()
+    def generate_batch(self, list_of_ids, steps=2000, kernel=True, cbhg_kernel=False, max_batch=8):
+        """`generate()` for a list of sentences: a list of (mel, linear, attention), one per sentence, as `generate()` returns them.
+
+        kernel=True (HIP device): the encoder and the post-net run per sentence as in `generate(kernel=True, cbhg_kernel=...)`; the decoder loops
+        run in groups of at most `max_batch` (1..8) sentences through `wrnn_taco_decode_batch` -- one persistent kernel per group, every
+        sentence ending on its own stop test, each result bit-identical to the single-sentence kernel's.  A sentence of more than
+        `_lib.TACO_BATCH_NMAX` ids goes through the single-sentence kernel.  kernel=False: a loop of `generate()`, on any device."""
+        from . import _lib
+        if not kernel:
+            return [self.generate(ids, steps=steps, kernel=False, cbhg_kernel=cbhg_kernel) for ids in list_of_ids]
+        if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
+            raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
+        dev = self.device
+        if dev.type != 'cuda':
+            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
+        self._bigru_kernel = True
+        front = bool(cbhg_kernel) and self._front_handle() is not None
+        self.last_front_path = 'hip' if front else 'torch'
+        encs = [(self.encode_kernel(ids)[:2] if front else self.encode(ids)) for ids in list_of_ids]
+        decoded = [None] * len(encs)
+        short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
+        for g in range(0, len(short), int(max_batch)):
+            group = short[g:g + int(max_batch)]
+            for i, d in zip(group, self._decode_batch_kernel([encs[i] for i in group], steps)):
+                decoded[i] = d
+        out = []
+        for i, e in enumerate(encs):
+            mel, attn = decoded[i] if decoded[i] is not None else self._decode_kernel(e[0], e[1], steps)
+            if front:
+                linear = self.postnet_kernel(mel)[0].transpose(0, 1)
+            else:
+                linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+            out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
+        return out
 
     @torch.no_grad()
     def generate(self, ids, steps=2000, kernel=False, kernel_variant=0, cbhg_kernel=False):
