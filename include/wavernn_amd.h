@@ -48,7 +48,7 @@ enum {
                                device of >= 256 CUs (a qualifying 9-bit RAW pack keeps the dense kernels: WRNN_ALGO_SPARSE runs it on request), else
                                WRNN_ALGO_CHAIN (<= 128 segments, >= 256 CUs), else WRNN_ALGO_DUO (>= 256 CUs: always its 4 clusters), else
                                WRNN_ALGO_LOOP (>= 64 CUs: 1 or 2 clusters; also when wrnn_options.clusters asks `auto` for fewer than 4), else -- and for
-                               RAW with another class count -- WRNN_ALGO_STREAM; other dims: wrnn_generic_kernel.  The planner's one table of the
+                               RAW with fewer classes -- WRNN_ALGO_STREAM; other dims, and RAW with more classes: wrnn_generic_kernel.  The planner's one table of the
                                kernels: KINDS in csrc/wrnn_abi.hip */
     WRNN_ALGO_STREAM = 1,   /* one workgroup per folded segment, weights streamed from L2/MALL each step: the generic fallback
                                (any class count, any device size) and the on-GPU cross-check */
@@ -84,7 +84,8 @@ typedef struct wrnn_weights {
     int32_t fc_dims;     /* F: 512 for the MFMA kernels; <= 2048 otherwise */
     int32_t feat_dims;   /* M: 80 for the MFMA kernels; feat + aux <= 1024 otherwise */
     int32_t aux_dims;    /* A: 32 for the MFMA kernels */
-    int32_t n_classes;   /* C: 30 (MOL) or 2**bits (RAW); shipped dims: RAW 2..512 classes (the loop kernel needs 512, others stream) */
+    int32_t n_classes;   /* C: 30 (MOL) or 2**bits (RAW), 2..2048; shipped dims: the loop kernels need 512, 2..511 stream, 513..2048 run on
+                            wrnn_generic_kernel like non-shipped dims */
     int32_t mode;        /* WRNN_MODE_* */
     const float *I_w, *I_b;                          /* I.weight (H,1+M+A), I.bias (H) */
     const float *w_ih1, *w_hh1, *b_ih1, *b_hh1;      /* rnn1.weight_ih_l0 (3H,H), weight_hh_l0 (3H,H), biases (3H) */

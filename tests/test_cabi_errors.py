@@ -44,6 +44,29 @@ def test_pack_create_argument_checks(L):
     assert L.wrnn_pack_create(ctypes.byref(w), 0, ctypes.byref(pack)) == ERR_ARG
 
 
+def test_pack_create_refuses_what_the_generic_kernel_cannot_take(L):
+    """The bounds of `generic_dims_ok` (csrc/wrnn_generic.hip) as include/wavernn_amd.h documents them: rnn, fc, RAW classes <= 2048, feat + aux <= 1024.
+    The dims are checked before any weight is read (the arrays here are those of the shipped dims) and before a device is looked for."""
+    sd = random_state_dict(1, mode='RAW')
+    pack = ctypes.c_void_p()
+    for over in (dict(rnn_dims=2049), dict(fc_dims=2049), dict(feat_dims=993), dict(feat_dims=40, aux_dims=985), dict(rnn_dims=256, n_classes=4096),
+                 dict(n_classes=4096)):                          # (the last: shipped dims -- more than 512 RAW classes are the generic kernel's too)
+        w, keep = _weights(sd, 'RAW', **over)
+        assert L.wrnn_pack_create(ctypes.byref(w), 0, ctypes.byref(pack)) == ERR_ARG, over
+        assert b'unsupported dims' in L.wrnn_last_error(), (over, L.wrnn_last_error())
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='needs a box WITHOUT a GPU')
+def test_dims_at_the_generic_bounds_pass_the_argument_checks(L):
+    """... and one step inside each bound the refusal is the missing device, not the dims: 2048 / 2048 / feat + aux = 1024 fit the kernel's 64 KB of LDS
+    with few classes, 2048 RAW classes with small dims, and the shipped dims with 1024 RAW classes are no argument error any more."""
+    sd = random_state_dict(1, mode='RAW')
+    pack = ctypes.c_void_p()
+    for over in (dict(rnn_dims=2048, fc_dims=2048, feat_dims=992, aux_dims=32, n_classes=2), dict(rnn_dims=256, n_classes=2048), dict(n_classes=1024)):
+        w, keep = _weights(sd, 'RAW', **over)                     # (the arrays are never read: no device, no pack)
+        assert L.wrnn_pack_create(ctypes.byref(w), 0, ctypes.byref(pack)) == ERR_NO_DEVICE, (over, L.wrnn_last_error())
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='needs a box WITHOUT a GPU')
 def test_no_device_is_an_error_not_a_fallback(L):
     sd = random_state_dict(1, mode='MOL')

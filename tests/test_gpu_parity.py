@@ -995,7 +995,9 @@ def test_non_shipped_hparams_run_on_the_generic_kernel(gpu, mode, tmp_path):
     """The reference's constructor takes any dims (models/fatchord_version.py:93-123; hparams.py:38-44 are defaults, `bits` is a
     CLI-visible hparam): rnn 256, fc 384, 8 bits, 40 mel bins, res_out 64 (aux 16), hop 128 run end to end through `generate()` on
     `wrnn_generic_kernel` and the HIP pre-loop kernels (round 5: wrnn_resnet_generic_kernel; no PyTorch-ROCm module runs) and
-    equal the oracle: RAW bit-exact, MoL <= MOL_TOL.  Round-2 verdict: every kernel rejected everything but the shipped dims."""
+    equal the oracle: RAW bit-exact, MoL <= MOL_TOL.  Round-2 verdict: every kernel rejected everything but the shipped dims.
+    This is the end-to-end path at one friendly geometry (every dim a multiple of 64 and below the workgroup's 512 threads); the kernel's edges -- odd
+    dims, more rows or classes than threads, F > H, A = 1, ragged segment tables -- are in tests/test_gpu_fallback_dims.py."""
     import warnings
     from oracle import c_oracle as C, wavernn_oracle as O
     from wavernn_amd.model import WaveRNN

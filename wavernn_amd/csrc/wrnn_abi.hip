@@ -129,12 +129,14 @@ struct Builder {
 extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **out)
 {
     if (!w || !out) { set_err("NULL argument"); return WRNN_ERR_ARG; }
-    const bool shipped = w->rnn_dims == H && w->fc_dims == H && w->feat_dims == MEL && w->aux_dims == AUX;
     const int C = w->n_classes;
+    // the shipped geometry -- what the MFMA kernels and the stream kernel are built for; RAW with more classes than the stream kernel has threads
+    // (bits > 9) takes the generic pack like any other non-shipped hparam
+    const bool shipped = w->rnn_dims == H && w->fc_dims == H && w->feat_dims == MEL && w->aux_dims == AUX && !(w->mode == WRNN_MODE_RAW && C > H);
     if (w->mode == WRNN_MODE_MOL) {
         if (C != 30) { set_err("MOL needs n_classes == 30"); return WRNN_ERR_ARG; }
     } else if (w->mode == WRNN_MODE_RAW) {
-        if (shipped && (C < 2 || C > H)) { set_err("RAW needs 2 <= n_classes <= 512 with the shipped dims"); return WRNN_ERR_ARG; }
+        if (shipped && C < 2) { set_err("RAW needs 2 <= n_classes <= 2048 (the shipped dims: up to 512 on the MFMA / stream kernels, more on the generic kernel)"); return WRNN_ERR_ARG; }
     } else { set_err("unknown mode %d", w->mode); return WRNN_ERR_ARG; }
     if (!shipped && !generic_dims_ok(w->rnn_dims, w->fc_dims, w->feat_dims, w->aux_dims, C, w->mode)) {
         set_err("unsupported dims rnn=%d fc=%d feat=%d aux=%d classes=%d: the generic kernel takes rnn, fc, classes <= 2048, feat + aux <= 1024 "
@@ -549,8 +551,8 @@ int default_slab(const Plan &pl, int mode, int C, bool noise_lib)
 //   else up to CHAIN_AUTO_GROUPS groups (128 segments), >= 256 CUs                           wrnn_chain_kernel
 //   else >= 256 CUs                                                                          wrnn_duo_kernel, always on 4 clusters
 //   else >= 64 CUs                                                                           wrnn_loop_kernel on 1 or 2 clusters, no more than there are groups
-//   else, and RAW with another class count                                                   wrnn_stream_kernel
-// non-shipped dims: wrnn_generic_kernel.  wrnn_duo_kernel on 1 or 2 clusters (>= 64 CUs) and wrnn_octo_kernel (MOL, >= 256 CUs) run on request only.
+//   else, and RAW with fewer classes                                                         wrnn_stream_kernel
+// non-shipped dims, and the shipped ones with more than 512 RAW classes (a generic pack): wrnn_generic_kernel. wrnn_duo_kernel on 1 or 2 clusters (>= 64 CUs) and wrnn_octo_kernel (MOL, >= 256 CUs) run on request only.
 // wrnn_options.depth is honoured up to the kernel's max_depth; .clusters (1, 2, 4) only where loop / duo / octo is planned (`auto` on fewer than 4
 // clusters: wrnn_loop_kernel).
 int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Plan *pl)
