@@ -158,6 +158,8 @@ typedef struct wrnn_options {
                                   sentinel instead of one word per 16-byte fragment (round 7; not in the phase-clock builds), bit 8 = every layer written
                                   through (no XCD-local plain stores), bit 14 = with phase_clocks: the stage time line of three steps as well
                                   (phase_clocks then holds [256 * 32 + 512 * 512] words; scripts/gpu_duo_trace.py);
+                                wrnn_duo / _chain / _sparse_kernel (read by the library, by no kernel): bit 13 = a slab's derived MoL noise, its aux tables and the clearing
+                                  of the placement words by three calls (two launches and a memset) instead of the one wrnn_slab_prep_kernel launch;
                                 wrnn_sparse_kernel, wrnn_chain_kernel: bits 2, 8 as wrnn_duo_kernel; wrnn_sparse_kernel: bit 11 = the DENSE fc stages on a pack whose
                                   Linear layers are block-sparse too, bit 4 = MOL with gathered fc stages: y2 published and fc3 run densely by the sampling
                                   workgroup instead of folded into the fc2 tiles (RAW: no effect -- y2 is always published); wrnn_chain_kernel: bit 5 = MoL's fc3 tiles read from LDS (round 5).
@@ -357,13 +359,36 @@ int wrnn_pre_hop(const wrnn_pre *p);                                   /* produc
 size_t wrnn_pre_workspace_bytes(const wrnn_pre *p, int32_t n_frames);
 /* mel: device [feat][n_frames] (the (1, feat, N) tensor generate() receives, fatchord_version.py:169,183);
  * mels_up: device [n_frames*hop][feat]; aux: device [n_frames][R] (per FRAME: the x hop Stretch2d repeat of :83-85 is
- * left to the loop).  Several utterances: call once per utterance with offset output pointers.  Asynchronous on `stream`. */
+ * left to the loop).  n_frames >= 1: ONE frame is the smallest utterance the stage takes (the `pad` frames each side are zeros it supplies itself);
+ * n_frames * hop <= 2e9.  Several utterances: wrnn_pre_upsample_many below (or one call per utterance with offset output pointers).
+ * Asynchronous on `stream`. */
 int wrnn_pre_upsample(const wrnn_pre *p, const float *mel, int32_t n_frames, float *mels_up, float *aux,
                       void *workspace, size_t workspace_bytes, void *stream);
 /* The same without the last Stretch2d + conv stage and its crop (ABI v6): mel_rows: device [(n_frames + 2 pad) * s0 * s1][feat], the input
  * of the last stage, which wrnn_duo_kernel then forms inside the loop (wrnn_options.mel_stage = 1); aux as above. */
 int wrnn_pre_upsample_rows(const wrnn_pre *p, const float *mel, int32_t n_frames, float *mel_rows, float *aux,
                            void *workspace, size_t workspace_bytes, void *stream);
+/* Several utterances in ONE call (appended to ABI v9: the symbols tell whether a library has them): a host table of utterances, each written into its
+ * slice of the concatenated outputs -- rows [up_row, up_row + n_frames * hop) of `mels_up` (rows_only: [up_row, up_row + (n_frames + 2 pad) * s0 * s1) of
+ * the mel_rows buffer) and rows [aux_row, aux_row + n_frames) of `aux`.  With the shipped hparams (80 / 128 / 128, pad 2, factors 5, 5, 11) every stage is
+ * ONE launch for all utterances: a workgroup finds (utterance, tile) through a small prefix table that the call stages and uploads into the workspace in
+ * one copy; an utterance keeps the tiles and grids wrnn_pre_upsample gives it and every output element the same summation order, so the result is
+ * BITWISE that of n_utt wrnn_pre_upsample / _rows calls.  Any other hparams: those n_utt calls, made here.  The slices must not overlap (not checked).
+ * WRNN_ERR_ARG -- before anything is launched -- for a NULL table, n_utt < 1, an n_frames < 1, a NULL mel, a negative offset, or a workspace smaller
+ * than wrnn_pre_workspace_bytes_many(same table, same rows_only) (0 for a bad table).  Asynchronous on `stream`; the table is read during the call only. */
+typedef struct wrnn_pre_utt {
+    const float *mel;             /* device [feat][n_frames] */
+    int32_t n_frames;
+    int32_t reserved;             /* 0 */
+    int64_t up_row;               /* first row of this utterance in mels_up / mel_rows ([row][feat]) */
+    int64_t aux_row;              /* first row (= frame) of this utterance in aux ([frame][R]) */
+} wrnn_pre_utt;
+size_t wrnn_pre_workspace_bytes_many(const wrnn_pre *p, const wrnn_pre_utt *utts, int32_t n_utt, int32_t rows_only);
+int wrnn_pre_upsample_many(const wrnn_pre *p, const wrnn_pre_utt *utts, int32_t n_utt, int32_t rows_only, float *mels_up, float *aux,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook: a handle holding the DIMS of `w` only (no device, no weights; no pointer of `w` is read): the size queries answer on it, and every entry
+ * point that would launch returns WRNN_ERR_NO_DEVICE on it BEHIND its argument checks -- which is what it is for, on a host without a device. */
+int wrnn_pre_debug_host_handle(const wrnn_pre_weights *w, wrnn_pre **out);
 const char *wrnn_pre_last_error(void);
 
 /*

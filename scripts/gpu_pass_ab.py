@@ -9,7 +9,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--mode', default='MOL'); ap.add_argument('--utterances', type=int, default=16); ap.add_argument('--passes', type=int, default=4)
 ap.add_argument('--prune', type=float, default=0.0); ap.add_argument('--prune-linear', action='store_true')
 ap.add_argument('--noise-chunk-mb', type=int, default=0, help='model.noise_chunk_bytes (0: the default)')
-ap.add_argument('--settings', default='1:0:1,8:1:1,8:1:0', help='pre_streams:pinned_output:mel_in_loop triples')
+ap.add_argument('--settings', default='1:0:1,8:1:1,8:1:0', help='pre_streams:pinned_output:mel_in_loop triples (pre_streams 0 = the batched pre-loop entry)')
 a = ap.parse_args()
 from wavernn_amd.model import WaveRNN
 from wavernn_amd.batch import generate_corpus
@@ -27,6 +27,7 @@ mels = [torch.from_numpy(random_mel(1234 + u, 641)).unsqueeze(0).to(dev) for u i
 for st in a.settings.split(','):
     ps, pin, mil = (int(x) for x in st.split(':'))
     m.pre_streams, m.pinned_output, m.mel_in_loop = ps, bool(pin), bool(mil)
+    m.pre_batched = ps == 0              # (pre_streams 0 here: the batched entry, wrnn_pre_upsample_many; else utterance by utterance)
     best, loop, tot = 1e9, 0.0, []
     for _ in range(a.passes + 1):
         torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -25,7 +25,8 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
            'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
-           'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_last_error',
+           'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_workspace_bytes_many',
+           'wrnn_pre_upsample_many', 'wrnn_pre_debug_host_handle', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
            'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch']
@@ -41,6 +42,12 @@ class PreWeights(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('feat_dims', 'compute_dims', 'res_out_dims', 'res_blocks', 'pad')] + \
                [('upsample_factors', ctypes.c_int32 * 3)] + \
                [(n, ctypes.c_void_p) for n in ('conv_in_w', 'bn_in', 'res_w', 'res_bn', 'conv_out_w', 'conv_out_b', 'up_w')]
+
+
+class PreUtt(ctypes.Structure):
+    """wrnn_pre_utt: one utterance of a `wrnn_pre_upsample_many` table."""
+    _fields_ = [('mel', ctypes.c_void_p), ('n_frames', ctypes.c_int32), ('reserved', ctypes.c_int32), ('up_row', ctypes.c_int64),
+                ('aux_row', ctypes.c_int64)]
 
 
 TACO_WEIGHT_FIELDS = ('prenet_fc1_w', 'prenet_fc1_b', 'prenet_fc2_w', 'prenet_fc2_b', 'attn_rnn_w_ih', 'attn_rnn_w_hh', 'attn_rnn_b_ih',
@@ -224,6 +231,11 @@ def lib():
     L.wrnn_pre_upsample.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.wrnn_pre_upsample_rows.argtypes = L.wrnn_pre_upsample.argtypes
+    L.wrnn_pre_workspace_bytes_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(PreUtt), ctypes.c_int32, ctypes.c_int32]
+    L.wrnn_pre_workspace_bytes_many.restype = ctypes.c_size_t
+    L.wrnn_pre_upsample_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(PreUtt), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.wrnn_pre_debug_host_handle.argtypes = [ctypes.POINTER(PreWeights), ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_pre_last_error.restype = ctypes.c_char_p
     L.wrnn_post_unfold.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,

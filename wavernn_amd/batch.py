@@ -263,6 +263,25 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
 
     out_local = torch.zeros(n_max, plan.T, dtype=torch.float32, device=device)
     native_pre = loop_fn is None and getattr(model, 'pre_algo', 'torch') == 'native' and device.type == 'cuda'
+    # the post-loop stage's share of the utterances is known from the plan: its tables go to the device now, in front of the loop, so that
+    # nothing but the unfold launch and the copy to the host follows the last loop launch (model.post_tables_early = False: behind the loop, A/B)
+    n_utt = len(frames)
+    mine_u = [u for u in range(n_utt) if finish != 'own' or (lo <= plan.first[u] < hi)]
+    local_u = [u for u in mine_u if lo <= plan.first[u] and plan.first[u] + plan.folds[u] <= hi]      # no segment on another rank
+    local_set = set(local_u)
+    rest_u = [u for u in mine_u if u not in local_set]
+    native_post = loop_fn is None and getattr(model, 'post_algo', 'numpy') == 'native' and out_local.is_cuda
+    slab_tuning = 8192 if getattr(model, 'slab_prep_split', False) else 0       # (wrnn_options.tuning bit 13: the three-call slab preparation, A/B)
+
+    def unfold_args(us, first_of):
+        return ([first_of(u) for u in us], [int(plan.folds[u]) for u in us], [(frames[u] - 1) * hop for u in us], overlap, hop, model.n_classes, mu_law, True)
+    first_local, first_all = (lambda u: int(plan.first[u]) - lo), (lambda u: int(plan.first[u]))
+    early = {}
+    if native_post and not return_segments and getattr(model, 'post_tables_early', True):
+        from .post import prepare_unfold
+        for us, first_of in ((local_u, first_local), (rest_u, first_all)):
+            if us and not (shard is not None and first_of is first_all):
+                early[first_of] = prepare_unfold(*unfold_args(us, first_of), device=device)
     with torch.no_grad():
         for utts, clo, chi in (chunk_utterances(plan, lo, hi, max_segments_per_launch) if hi > lo else []):
             # conditioning of the utterances this chunk touches, concatenated (each starts on a frame boundary)
@@ -289,7 +308,8 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                             r0 += n_rows[k]
                         else:
                             jobs.append((mels[u], mels_up[a0:a0 + frames[u] * hop], aux[a0 // hop:a0 // hop + frames[u]]))
-                    pre.upsample_many(jobs, rows=rows, streams=int(getattr(model, 'pre_streams', 8)))      # (the utterances side by side on side streams)
+                    pre.upsample_many(jobs, rows=rows, streams=int(getattr(model, 'pre_streams', 8)),
+                                      batched=bool(getattr(model, 'pre_batched', True)))      # (batched: one launch per stage for all of them)
                     if rows:       # utterance k of the chunk: its rows start 2 * indent * k samples later than its cropped samples do
                         from .engine import MelRows
                         indent, order = pre.pad * hop, {u: k for k, u in enumerate(utts)}
@@ -364,7 +384,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for t0 in range(0, T, steps):
                     t1 = min(T, t0 + steps)
                     eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(t1 - t0), hop, algo=model.loop_algo, check=check, out=out_view,
-                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1), sparse_groups=groups, **lib_kw)
+                                     t_range=None if (t0 == 0 and t1 == T) else (t0, t1), sparse_groups=groups, tuning=slab_tuning, **lib_kw)
             except ResidencyError as e:
                 # the persistent grid was refused (on the first slice: a continuation cannot change kernels).  The other loop kernels read
                 # the up-sampled mel in full; the engine then degrades as usual on an unsliced call (one workgroup per CU, then the
@@ -376,7 +396,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
                 for u in gens:
                     gens[u].manual_seed(int(seeds[u]))
                     burn_ctor_draws(model.rnn_dims, model.aux_dims, 'cpu', gens[u])
-                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view, sparse_groups=groups, **lib_kw)
+                eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(T), hop, algo=model.loop_algo, check=check, out=out_view, sparse_groups=groups, tuning=slab_tuning, **lib_kw)
             finally:
                 if pool is not None:
                     pool.shutdown()
@@ -409,12 +429,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
         model.train()
     if return_segments:
         return gathered_segments().cpu().numpy().astype(np.float64), plan
-    mine_u = [u for u in range(n_utt) if finish != 'own' or (lo <= plan.first[u] < hi)]
-    local_u = [u for u in mine_u if lo <= plan.first[u] and plan.first[u] + plan.folds[u] <= hi]      # no segment on another rank
-    local_set = set(local_u)
-    rest_u = [u for u in mine_u if u not in local_set]
     outs = [None] * n_utt
-    native_post = loop_fn is None and getattr(model, 'post_algo', 'numpy') == 'native' and out_local.is_cuda
 
     def unfold(segs, first_of, us):
         """Post-loop stage (reference :245-260, :342-405) of utterances `us`, whose first segment is row first_of(u) of `segs`."""
@@ -422,8 +437,7 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
             return
         if native_post:       # on the device (float64, reference order): one launch for all of them
             from .post import unfold_on_device
-            wav, sl = unfold_on_device(segs, [first_of(u) for u in us], [int(plan.folds[u]) for u in us],
-                                       [(frames[u] - 1) * hop for u in us], overlap, hop, model.n_classes, mu_law, True)
+            wav, sl = unfold_on_device(segs, *unfold_args(us, first_of), tables=early.get(first_of))
             if getattr(model, 'pinned_output', True):
                 # the finished audio (8 B per sample) into page-locked memory at the link's rate (a pageable copy is staged through bounce buffers);
                 # torch's caching host allocator hands the pages back to the next call; the returned arrays are views that keep the buffer alive
@@ -445,13 +459,13 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
             outs[u] = _fold.finish_waveform(y, (frames[u] - 1) * hop, hop)
 
     t_u = time.perf_counter()
-    unfold(out_local, lambda u: int(plan.first[u]) - lo, local_u)          # under the all-gather
+    unfold(out_local, first_local, local_u)          # under the all-gather
     if timings is not None:
         timings['unfold_under_gather_ms'] = timings.get('unfold_under_gather_ms', 0.0) + (time.perf_counter() - t_u) * 1e3
     if shard is not None:
         return outs
     if rest_u:
-        unfold(gathered_segments(), lambda u: int(plan.first[u]), rest_u)
+        unfold(gathered_segments(), first_all, rest_u)
     elif work is not None:
         t_w = time.perf_counter()
         work.wait()

@@ -15,6 +15,7 @@ namespace wrnn {
 hipError_t launch_cond(const CondArgs &a, int n_cus, bool valu, hipStream_t stream);
 hipError_t launch_cond_frames(const CondArgs &a, hipStream_t stream);
 hipError_t launch_cond_frames_slab(const CondArgs &a, hipStream_t stream);
+hipError_t launch_slab_prep(const CondArgs &a, const float *nz_in, float *nz_out, long nz_n, unsigned *xcc, int n_cus, hipStream_t stream);
 hipError_t launch_cond_frag(const CondArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_noise_mol(const float *in, float *out, long n, int B, int n_cus, hipStream_t stream);
 hipError_t launch_noise_fill(bool mol, int B, int C, int t0, int t1, uint64_t seed, const uint64_t *seg_id, float *out, int n_cus, hipStream_t stream);
@@ -935,9 +936,14 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
             // wrnn_options.noise_lib: this slab's noise, drawn into the workspace in front of its launches -- what the caller's tensor holds in rows
             // [s0 - t_begin, s1 - t_begin)
             if (lib_noise) HIPCHK(launch_noise_fill(mol, B, p->tr.C, s0, s1, o->noise_seed, o->noise_seg_id, (float *)(ws + l.nlib), p->tr.n_cus, stream));
+            // a slabbed kernel: derived noise, aux tables and the placement words of the slab's first launch in one launch (wrnn_slab_prep_kernel);
+            // wrnn_options.tuning bit 13: by the three calls below, as before (A/B)
+            const bool prep_fused = k.slabbed && !(o->tuning & 8192);
+            const float *mol_rows = nullptr;
             if (mol) {   // noise rows are relative to t_begin (wrnn_options.t_begin)
                 const float *const rows = lib_noise ? (const float *)(ws + l.nlib) : noise + (size_t)(s0 - pl.t0) * 11 * B;
-                HIPCHK(launch_noise_mol(rows, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->tr.n_cus, stream));
+                if (prep_fused) mol_rows = rows;
+                else HIPCHK(launch_noise_mol(rows, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, B, p->tr.n_cus, stream));
                 a.noise_pre = (const float *)(ws + l.npre);
                 a.noise_t0 = s0;
             } else if (lib_noise) {
@@ -948,9 +954,11 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
             }
             if (k.slabbed) {   // this slab's aux tables of every segment of the call
                 c.t0 = s0; c.B = B; c.FPS = pl.tab_fps;
-                HIPCHK(launch_cond_frames_slab(c, stream));
+                if (prep_fused) HIPCHK(launch_slab_prep(c, mol_rows, (float *)(ws + l.npre), (long)(s1 - s0) * 11 * B, (unsigned *)(ws + l.xcc), p->tr.n_cus, stream));
+                else HIPCHK(launch_cond_frames_slab(c, stream));
                 a.tab_fps = pl.tab_fps; a.tab_t0 = s0;
             }
+            bool xcc_clear = prep_fused;      // (the placement words of the slab's FIRST launch are cleared by the prep kernel)
             for (int r = 0; r < pl.rounds; ++r) {
                 const int rb0 = (int)(((long)r * B) / pl.rounds), rb1 = (int)(((long)(r + 1) * B) / pl.rounds);
                 const int nr = rb1 - rb0;
@@ -962,7 +970,8 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
                 // (every step re-arms the entries it will write two or three steps later), so it needs the fill only where a round starts: the first
                 // launch of a call that starts at step 0, or any launch when several rounds share the buffer
                 if (!k.slabbed || s0 == 0 || pl.rounds > 1 || (o->tuning & 4)) HIPCHK(hipMemsetAsync(ws + l.xbuf, 0xFF, k.xbuf_fill(pl.G), stream));
-                if (k.slabbed) HIPCHK(hipMemsetAsync(ws + l.xcc, 0, XCC_WORDS * sizeof(unsigned), stream));      // placement handshake of this launch
+                if (k.slabbed && !xcc_clear) HIPCHK(hipMemsetAsync(ws + l.xcc, 0, XCC_WORDS * sizeof(unsigned), stream));      // placement handshake of this launch
+                xcc_clear = false;
                 a.state = (float *)(ws + l.state) + (size_t)r * k.state_floats(pl.G);
                 a.t0 = s0; a.t1 = s1; a.cI_t0 = s0; a.rb0 = rb0; a.Btot = nr; a.NG = ngr; a.resume = s0 > 0 ? 1 : 0;
                 a.kind_tag = k.kind_tag;

@@ -260,14 +260,99 @@ __global__ __launch_bounds__(H) void wrnn_cond_frame_slab_kernel(const CondArgs 
 // MOL sampling noise -> the two derived variates the sampler needs (utils/distribution.py:106-108,118-121), once per
 // launch instead of once per workgroup and step: mixture columns u -> log(-log u) (Gumbel), logistic column
 // u -> log u - log(1-u).  Same device math functions and operation order as the in-loop form (mol_gumbel / mol_sample).
-__global__ __launch_bounds__(256) void wrnn_noise_mol_kernel(const float *__restrict__ in, float *__restrict__ out, long n, int B)
+__device__ __forceinline__ void noise_mol_body(const float *__restrict__ in, float *__restrict__ out, long n, int B, long i0, long stride)
 {
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    for (long i = i0; i < n; i += stride) {
         const float u = in[i];
         const int col = (int)(i % (11L * B));
         out[i] = (col < 10 * B) ? logf(-logf(u)) : (logf(u) - logf(1.0f - u));
     }
+}
+__global__ __launch_bounds__(256) void wrnn_noise_mol_kernel(const float *__restrict__ in, float *__restrict__ out, long n, int B)
+{
+    noise_mol_body(in, out, n, B, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+}
+
+// Everything a slabbed loop kernel (wrnn_duo / _chain / _sparse_kernel) needs in front of a slab's first launch, in ONE launch: workgroups
+// [0, cond_blocks) fill the slab's per-segment aux tables (wrnn_cond_frame_slab_kernel's rows, SPR rows per workgroup: a thread's 160 weights are
+// read once for SPR rows instead of once per row -- 2049 rows x 320 KB of L2 reads become 257 x 320 KB; every output is the same fmaf chain, k
+// ascending, then the bias); the workgroups behind them derive the MoL noise (wrnn_noise_mol_kernel's element-wise form; RAW: one workgroup,
+// nz_n = 0), and the first of those also clears the placement words of the launch that follows.  Three calls (two launches and a memset) before:
+// wrnn_options.tuning bit 13 brings them back for A/B.
+constexpr int SPR = 8;
+struct SlabPrepArgs {
+    CondArgs c;                         // as for wrnn_cond_frame_slab_kernel (t0, B, FPS)
+    const float *nz_in;                 // MOL: the slab's noise rows [steps][11 B]
+    float *nz_out;
+    long nz_n;                          // elements (0: no noise to derive)
+    unsigned *xcc;                      // [XCC_WORDS] placement words
+    int cond_blocks, nz_blocks;
+};
+__global__ __launch_bounds__(H) void wrnn_slab_prep_kernel(const SlabPrepArgs s)
+{
+    const int r = threadIdx.x;
+    if ((int)blockIdx.x >= s.cond_blocks) {
+        const int nb = (int)blockIdx.x - s.cond_blocks;
+        if (nb == 0)
+            for (int i = r; i < XCC_WORDS; i += H) s.xcc[i] = 0u;
+        noise_mol_body(s.nz_in, s.nz_out, s.nz_n, s.c.B, (long)nb * H + r, (long)s.nz_blocks * H);
+        return;
+    }
+    const CondArgs &a = s.c;
+    __shared__ float ax[SPR][4 * AUX];
+    const int nrows = a.B * a.FPS + 1, row0 = (int)blockIdx.x * SPR;
+    for (int q = r; q < SPR * 4 * AUX; q += H) {
+        const int i = q / (4 * AUX), e = q % (4 * AUX), row = row0 + i;
+        int f = a.NF;                                       // (the last row, and the rows past it: zero conditioning)
+        if (row < a.B * a.FPS) {
+            const int b = row / a.FPS, j = row % a.FPS;
+            f = (a.seg_pos[b] + a.t0) / a.hop + j;
+        }
+        ax[i][e] = (f < a.NF) ? a.aux[(size_t)f * 4 * AUX + e] : 0.f;
+    }
+    __syncthreads();
+    float g0[SPR], g1[SPR], g2[SPR], y3[SPR], y4[SPR];
+#pragma unroll
+    for (int i = 0; i < SPR; ++i) { g0[i] = 0.f; g1[i] = 0.f; g2[i] = 0.f; y3[i] = 0.f; y4[i] = 0.f; }
+#pragma unroll 4
+    for (int k = 0; k < AUX; ++k) {
+        const float w0 = a.c2_wT[k * 3 * H + r], w1 = a.c2_wT[k * 3 * H + H + r], w2 = a.c2_wT[k * 3 * H + 2 * H + r];
+        const float w3 = a.c3_wT[k * H + r], w4 = a.c4_wT[k * H + r];
+#pragma unroll
+        for (int i = 0; i < SPR; ++i) {
+            g0[i] = fmaf(w0, ax[i][AUX + k], g0[i]);
+            g1[i] = fmaf(w1, ax[i][AUX + k], g1[i]);
+            g2[i] = fmaf(w2, ax[i][AUX + k], g2[i]);
+            y3[i] = fmaf(w3, ax[i][2 * AUX + k], y3[i]);
+            y4[i] = fmaf(w4, ax[i][3 * AUX + k], y4[i]);
+        }
+    }
+    const float b0 = a.b_ih2[r], b1 = a.b_ih2[H + r], b2 = a.b_ih2[2 * H + r], b3 = a.fc1_b[r], b4 = a.fc2_b[r];
+#pragma unroll
+    for (int i = 0; i < SPR; ++i) {
+        const int row = row0 + i;
+        if (row < nrows) {
+            a.c2f[(size_t)row * 3 * H + r] = g0[i] + b0;
+            a.c2f[(size_t)row * 3 * H + H + r] = g1[i] + b1;
+            a.c2f[(size_t)row * 3 * H + 2 * H + r] = g2[i] + b2;
+            a.c3f[(size_t)row * H + r] = y3[i] + b3;
+            a.c4f[(size_t)row * H + r] = y4[i] + b4;
+        }
+    }
+}
+
+// a.t0 / a.B / a.FPS as for launch_cond_frames_slab; nz_in = nullptr: no noise to derive (RAW)
+hipError_t launch_slab_prep(const CondArgs &a, const float *nz_in, float *nz_out, long nz_n, unsigned *xcc, int n_cus, hipStream_t stream)
+{
+    SlabPrepArgs s;
+    s.c = a; s.nz_in = nz_in; s.nz_out = nz_out; s.nz_n = nz_in ? nz_n : 0; s.xcc = xcc;
+    s.cond_blocks = (a.B * a.FPS + 1 + SPR - 1) / SPR;
+    long nb = (s.nz_n + H - 1) / H;
+    if (nb > (long)n_cus * 4) nb = (long)n_cus * 4;
+    if (nb < 1) nb = 1;
+    s.nz_blocks = (int)nb;
+    hipLaunchKernelGGL(wrnn_slab_prep_kernel, dim3((unsigned)(s.cond_blocks + s.nz_blocks)), dim3(H), 0, stream, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_noise_mol(const float *in, float *out, long n, int B, int n_cus, hipStream_t stream)

@@ -14,6 +14,10 @@
 //          reference's constructor takes (:64-71; hparams.py:38-44 are only defaults) -- a tile of frames per workgroup in LDS, one output
 //          per thread and trip, k ascending in one fmaf chain; the up-sampling stages take the channel count at run time (F = 0).  The
 //          shipped dims keep the MFMA kernel.
+// K-pre-many wrnn_resnet_many_kernel, wrnn_upstage_many_kernel, wrnn_upstage_last_many_kernel (wrnn_pre_upsample_many): the same stages for a TABLE of
+//          utterances, one launch per stage for all of them (16 x 641 frames: 4 launches behind one library call instead of 64 behind 16, on side streams).
+//          The bodies are the device functions the per-utterance kernels call (resnet_tile, upstage_body, upstage_last_body); block -> (utterance,
+//          tile) through PreUttDev.blk, an utterance keeping the grid pre_run gives it: the same bits.  Shipped hparams only.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -66,13 +70,15 @@ __device__ __forceinline__ f32x4 pre_tile(const float *W, int ld, int kvalid, in
     return total;
 }
 
-__global__ __launch_bounds__(256) void wrnn_resnet_kernel(const PreArgs a)
+// one tile of PNF frames of ONE utterance (a.mel / a.aux / a.N) through the whole network: the body of wrnn_resnet_kernel and of
+// wrnn_resnet_many_kernel (the same code, hence the same bits, whichever launch a tile belongs to)
+__device__ __forceinline__ void resnet_tile(const PreArgs &a, int tile)
 {
     __shared__ __attribute__((aligned(16))) float XIN[PNF * PLDI];
     __shared__ __attribute__((aligned(16))) float XA[PNF * PLDX];
     __shared__ __attribute__((aligned(16))) float XB[PNF * PLDX];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j0 = blockIdx.x * PNF;                       // first output frame of this tile
+    const int j0 = tile * PNF;                             // first output frame of this tile
     const int N = a.N;
     // im2col of the zero-padded mel (:185 pads `pad` frames each side): XIN[j][c*5 + t] = m[c][j0 + j + t - pad]
     for (int q = tid; q < PNF * PLDI; q += 256) {
@@ -142,6 +148,41 @@ __global__ __launch_bounds__(256) void wrnn_resnet_kernel(const PreArgs a)
     }
 }
 
+__global__ __launch_bounds__(256) void wrnn_resnet_kernel(const PreArgs a) { resnet_tile(a, blockIdx.x); }
+
+// Several utterances in one launch (wrnn_pre_upsample_many): entry u of the device table holds utterance u's pointers and the first block
+// it owns in each of the four stage grids; entry n_utt holds the grids' sizes.  A workgroup finds its utterance by bisection (block-uniform).
+struct PreUttDev {
+    const float *mel;             // [PFEAT][n]
+    float *up, *aux;              // this utterance's slices of the concatenated outputs
+    float *s1, *s2;               // its intermediate stages in the workspace
+    int n;                        // frames
+    int blk[4];                   // first block in the grids of: MelResNet, stage 1, stage 2, last stage
+    int pad_;
+};
+static_assert(sizeof(PreUttDev) == 64, "table entry");
+struct PreManyArgs {
+    PreArgs w;                    // the weights (mel / aux / N: per utterance, from the table)
+    const PreUttDev *utt;         // [n_utt + 1]
+    int n_utt;
+};
+__device__ __forceinline__ int pre_find_utt(const PreUttDev *utt, int n_utt, int stage, int block)
+{
+    int lo = 0, hi = n_utt;                                // utt[lo].blk <= block < utt[hi].blk
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (utt[mid].blk[stage] <= block) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void wrnn_resnet_many_kernel(const PreManyArgs m)
+{
+    const int u = pre_find_utt(m.utt, m.n_utt, 0, blockIdx.x);
+    PreArgs a = m.w;
+    a.mel = m.utt[u].mel; a.aux = m.utt[u].aux; a.N = m.utt[u].n;
+    resnet_tile(a, blockIdx.x - m.utt[u].blk[0]);
+}
+
 // MelResNet for any dims (see the header).  Dynamic LDS: MW[feat][gf + 2 pad] (the zero-padded mel window of the tile: :185 pads `pad` frames
 // each side, conv_in has no padding of its own, :35), XA[gf][C], XB[gf][C].  Thread -> (row c, frame j) with j fastest: a wave reads one or a
 // few weight rows (broadcast) and consecutive LDS words.
@@ -204,16 +245,17 @@ __global__ __launch_bounds__(256) void wrnn_resnet_generic_kernel(const GenPreAr
 // LAST:  writes out_t[q - indent][c] for indent <= q < n_out - indent (the crop of :88, transposed to [sample][channel]).
 // S > 0: the stretch factor as a compile-time constant (the divisions become multiplies); S = 0: runtime `s_rt`.  F: the channel count
 // (PFEAT), F = 0: runtime `feat_rt`.
-template <bool FIRST, bool LAST, int S, int F = PFEAT>
-__global__ __launch_bounds__(256) void wrnn_upstage_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                           const float *__restrict__ taps, int n_in, int s_rt, int pad, int indent, int feat_rt = PFEAT)
+// (block `blk` of `nblk`: the launch's own grid, or an utterance's share of the batched launch -- an output element is the same fmaf chain in either)
+template <bool FIRST, bool LAST, int S, int F>
+__device__ __forceinline__ void upstage_body(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ taps, int n_in, int s_rt,
+                                             int pad, int indent, int feat_rt, long blk, long nblk)
 {
     const int s = S > 0 ? S : s_rt;
     const int feat = F > 0 ? F : feat_rt;
     const long n_out = (long)n_in * s;
     const long total = LAST ? (n_out - 2L * indent) * feat : n_out * feat;
     const int ld_in = FIRST ? n_in - 2 * pad : n_in;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    for (long idx = blk * blockDim.x + threadIdx.x; idx < total; idx += nblk * blockDim.x) {
         int c;
         long q;
         if (LAST) { c = (int)(idx % feat); q = idx / feat + indent; }
@@ -234,6 +276,23 @@ __global__ __launch_bounds__(256) void wrnn_upstage_kernel(const float *__restri
         else out[(size_t)c * n_out + q] = acc;
     }
 }
+template <bool FIRST, bool LAST, int S, int F = PFEAT>
+__global__ __launch_bounds__(256) void wrnn_upstage_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                           const float *__restrict__ taps, int n_in, int s_rt, int pad, int indent, int feat_rt = PFEAT)
+{
+    upstage_body<FIRST, LAST, S, F>(in, out, taps, n_in, s_rt, pad, indent, feat_rt, blockIdx.x, gridDim.x);
+}
+// The shipped hparams' stages 1 and 2 of several utterances (stage 1: FIRST; stage 2: LAST = the `_rows` form, which ends there).
+template <bool FIRST, bool LAST, int S>
+__global__ __launch_bounds__(256) void wrnn_upstage_many_kernel(const PreUttDev *__restrict__ utt, int n_utt, const float *__restrict__ taps)
+{
+    constexpr int stage = FIRST ? 1 : 2;
+    const int u = pre_find_utt(utt, n_utt, stage, blockIdx.x);
+    const int nf = utt[u].n + 2 * PPAD, n_in = FIRST ? nf : nf * 5;
+    const float *in = FIRST ? utt[u].mel : utt[u].s1;
+    float *out = FIRST ? utt[u].s1 : (LAST ? utt[u].up : utt[u].s2);
+    upstage_body<FIRST, LAST, S, PFEAT>(in, out, taps, n_in, S, PPAD, 0, PFEAT, blockIdx.x - utt[u].blk[stage], utt[u + 1].blk[stage] - utt[u].blk[stage]);
+}
 
 // The LAST stage through an LDS tile (round 3): wrnn_upstage_kernel<.., true, ..> maps consecutive threads to consecutive CHANNELS of
 // one sample (the output is [sample][channel]), so each of its 2 s + 1 reads per output walks 80 different rows of the input --
@@ -241,14 +300,14 @@ __global__ __launch_bounds__(256) void wrnn_upstage_kernel(const float *__restri
 // tile with consecutive threads on consecutive SAMPLES of one channel (a wave touches ~7 input words), parks it in LDS and
 // writes it out row by row, coalesced.  Same taps in the same order per output: bit-identical values.
 template <int S>
-__global__ __launch_bounds__(256) void wrnn_upstage_last_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                                const float *__restrict__ taps, int n_in, int s_rt, int indent)
+__device__ __forceinline__ void upstage_last_body(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ taps, int n_in, int s_rt,
+                                                  int indent, long blk, long nblk)
 {
     constexpr int TQ = 64;
     __shared__ float tile[TQ][PFEAT + 1];
     const int s = S > 0 ? S : s_rt;
     const long n_out = (long)n_in * s, nq = n_out - 2L * indent;
-    for (long q0 = (long)blockIdx.x * TQ; q0 < nq; q0 += (long)gridDim.x * TQ) {
+    for (long q0 = blk * TQ; q0 < nq; q0 += nblk * TQ) {
         for (int e = threadIdx.x; e < TQ * PFEAT; e += 256) {
             const int c = e / TQ, ql = e % TQ;
             const long q = q0 + ql + indent;
@@ -271,6 +330,18 @@ __global__ __launch_bounds__(256) void wrnn_upstage_last_kernel(const float *__r
         }
         __syncthreads();
     }
+}
+template <int S>
+__global__ __launch_bounds__(256) void wrnn_upstage_last_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                                const float *__restrict__ taps, int n_in, int s_rt, int indent)
+{
+    upstage_last_body<S>(in, out, taps, n_in, s_rt, indent, blockIdx.x, gridDim.x);
+}
+template <int S>
+__global__ __launch_bounds__(256) void wrnn_upstage_last_many_kernel(const PreUttDev *__restrict__ utt, int n_utt, const float *__restrict__ taps, int indent)
+{
+    const int u = pre_find_utt(utt, n_utt, 3, blockIdx.x);
+    upstage_last_body<S>(utt[u].s2, utt[u].up, taps, (utt[u].n + 2 * PPAD) * 25, S, indent, blockIdx.x - utt[u].blk[3], utt[u + 1].blk[3] - utt[u].blk[3]);
 }
 
 }  // namespace wrnn
@@ -303,24 +374,56 @@ struct wrnn_pre {
 
 static size_t generic_lds_bytes(int feat, int C, int pad, int gf) { return ((size_t)feat * (gf + 2 * pad) + 2 * (size_t)gf * C) * sizeof(float); }
 
-extern "C" int wrnn_pre_create(const wrnn_pre_weights *w, int device, wrnn_pre **out)
+// the dims of `w` (no pointer of it is read); *gf_out: wrnn_pre.gf
+static int pre_check_dims(const wrnn_pre_weights *w, int *gf_out)
 {
-    if (!w || !out) PRE_FAIL(WRNN_ERR_ARG, "NULL argument");
     if (w->feat_dims < 1 || w->feat_dims > 4096 || w->compute_dims < 1 || w->compute_dims > 4096 || w->res_out_dims < 1 || w->res_out_dims > 4096 ||
         w->pad < 0 || w->pad > 64 || w->res_blocks < 0 || w->res_blocks > 64)
         PRE_FAIL(WRNN_ERR_ARG, "bad UpsampleNetwork dims: feat_dims %d, compute_dims %d, res_out_dims %d, pad %d, res_blocks %d", w->feat_dims,
                  w->compute_dims, w->res_out_dims, w->pad, w->res_blocks);
     for (int i = 0; i < 3; ++i)
         if (w->upsample_factors[i] < 1 || w->upsample_factors[i] > 64) PRE_FAIL(WRNN_ERR_ARG, "bad upsample factor %d", w->upsample_factors[i]);
-    if (!w->conv_in_w || !w->bn_in || (w->res_blocks && (!w->res_w || !w->res_bn)) || !w->conv_out_w || !w->conv_out_b || !w->up_w)
-        PRE_FAIL(WRNN_ERR_ARG, "NULL weight pointer");
-    const int FE = w->feat_dims, C = w->compute_dims, R = w->res_out_dims, PD = w->pad, KT = 2 * PD + 1;
+    const int FE = w->feat_dims, C = w->compute_dims, R = w->res_out_dims, PD = w->pad;
     const bool shipped_dims = FE == PFEAT && C == PC && R == PC && PD == PPAD;
     int gf = 0;
     if (!shipped_dims) {                                        // the largest frame tile whose LDS fits the default 64 KB
         for (gf = 16; gf >= 1 && generic_lds_bytes(FE, C, PD, gf) > 65536; gf >>= 1) {}
         if (gf < 1) PRE_FAIL(WRNN_ERR_ARG, "UpsampleNetwork too wide for the pre-loop kernel (feat_dims %d, compute_dims %d, pad %d)", FE, C, PD);
     }
+    *gf_out = gf;
+    return WRNN_OK;
+}
+
+static void pre_set_dims(wrnn_pre *p, const wrnn_pre_weights *w, int device, int gf)
+{
+    p->device = device; p->blocks = w->res_blocks; p->total_scale = 1;
+    p->feat = w->feat_dims; p->C = w->compute_dims; p->R = w->res_out_dims; p->pad = w->pad; p->gf = gf;
+    for (int i = 0; i < 3; ++i) { p->scales[i] = w->upsample_factors[i]; p->total_scale *= w->upsample_factors[i]; }
+}
+
+// Test hook: a handle that holds the DIMS of `w` and nothing else (no device, no weights; no pointer of `w` is read).  The size queries answer on it;
+// every entry point that would launch fails on it with WRNN_ERR_NO_DEVICE -- behind its argument checks, which is what the handle is for.
+extern "C" int wrnn_pre_debug_host_handle(const wrnn_pre_weights *w, wrnn_pre **out)
+{
+    if (!w || !out) PRE_FAIL(WRNN_ERR_ARG, "NULL argument");
+    int gf = 0;
+    const int rc = pre_check_dims(w, &gf);
+    if (rc != WRNN_OK) return rc;
+    wrnn_pre *p = new wrnn_pre();
+    pre_set_dims(p, w, -1, gf);
+    *out = p;
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_pre_create(const wrnn_pre_weights *w, int device, wrnn_pre **out)
+{
+    if (!w || !out) PRE_FAIL(WRNN_ERR_ARG, "NULL argument");
+    int gf = 0;
+    const int rc_dims = pre_check_dims(w, &gf);
+    if (rc_dims != WRNN_OK) return rc_dims;
+    if (!w->conv_in_w || !w->bn_in || (w->res_blocks && (!w->res_w || !w->res_bn)) || !w->conv_out_w || !w->conv_out_b || !w->up_w)
+        PRE_FAIL(WRNN_ERR_ARG, "NULL weight pointer");
+    const int FE = w->feat_dims, C = w->compute_dims, R = w->res_out_dims, PD = w->pad, KT = 2 * PD + 1;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device >= n) PRE_FAIL(WRNN_ERR_NO_DEVICE, "no HIP device %d (count %d)", device, n);
     DeviceGuard dg(device);
@@ -348,9 +451,7 @@ extern "C" int wrnn_pre_create(const wrnn_pre_weights *w, int device, wrnn_pre *
     for (int i = 0; i < 3; ++i) { o_t[i] = put(w->up_w + toff, 2 * w->upsample_factors[i] + 1); toff += 2 * w->upsample_factors[i] + 1; }
     put(nullptr, 64);
     wrnn_pre *p = new wrnn_pre();
-    p->device = device; p->blocks = B; p->total_scale = 1;
-    p->feat = FE; p->C = C; p->R = R; p->pad = PD; p->gf = gf;
-    for (int i = 0; i < 3; ++i) { p->scales[i] = w->upsample_factors[i]; p->total_scale *= w->upsample_factors[i]; }
+    pre_set_dims(p, w, device, gf);
     hipError_t e = hipMalloc((void **)&p->dev, h.size() * 4);
     if (e != hipSuccess) { delete p; PRE_FAIL(WRNN_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
     e = hipMemcpy(p->dev, h.data(), h.size() * 4, hipMemcpyHostToDevice);
@@ -365,7 +466,7 @@ extern "C" int wrnn_pre_create(const wrnn_pre_weights *w, int device, wrnn_pre *
 extern "C" void wrnn_pre_destroy(wrnn_pre *p)
 {
     if (!p) return;
-    (void)hipFree(p->dev);
+    if (p->dev) (void)hipFree(p->dev);
     delete p;
 }
 
@@ -386,6 +487,7 @@ static int pre_run(const wrnn_pre *p, const float *mel, int32_t n_frames, float 
     if (n_frames < 1 || (double)n_frames * p->total_scale > 2.0e9) PRE_FAIL(WRNN_ERR_ARG, "bad n_frames %d", n_frames);
     if (workspace_bytes < wrnn_pre_workspace_bytes(p, n_frames)) PRE_FAIL(WRNN_ERR_WORKSPACE, "workspace too small");
     if (((uintptr_t)workspace & 255) != 0) PRE_FAIL(WRNN_ERR_ARG, "workspace must be 256-byte aligned");
+    if (p->device < 0) PRE_FAIL(WRNN_ERR_NO_DEVICE, "a dims-only handle (wrnn_pre_debug_host_handle) launches nothing");
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard dg(p->device);
     PRE_HIP(dg.err);
@@ -442,4 +544,103 @@ extern "C" int wrnn_pre_upsample_rows(const wrnn_pre *p, const float *mel, int32
                                       void *workspace, size_t workspace_bytes, void *stream)
 {
     return pre_run(p, mel, n_frames, mel_rows, aux, workspace, workspace_bytes, stream, true);
+}
+
+// ---- several utterances per call (appended to ABI v9) ------------------------------------------------------------------------------------------------
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the shipped hparams: the MFMA MelResNet and the (5, 5, 11) stages -- what the batched kernels are built for
+static bool pre_many_batched(const wrnn_pre *p) { return p->gf == 0 && p->scales[0] == 5 && p->scales[1] == 5 && p->scales[2] == 11; }
+// workspace of ONE utterance behind the table: batched: stage 1 [, stage 2], each on a 256-byte boundary; else what wrnn_pre_upsample takes
+static size_t pre_many_slice(const wrnn_pre *p, int32_t n_frames, bool rows_only, size_t *s2_off)
+{
+    if (!pre_many_batched(p)) return al256(wrnn_pre_workspace_bytes(p, n_frames));
+    const size_t nf = (size_t)n_frames + 2 * p->pad, s1 = al256(nf * p->scales[0] * p->feat * sizeof(float));
+    if (s2_off) *s2_off = s1;
+    return s1 + (rows_only ? 0 : al256(nf * p->scales[0] * p->scales[1] * p->feat * sizeof(float)));
+}
+
+extern "C" size_t wrnn_pre_workspace_bytes_many(const wrnn_pre *p, const wrnn_pre_utt *utts, int32_t n_utt, int32_t rows_only)
+{
+    if (!p || !utts || n_utt < 1) return 0;
+    size_t total = al256((size_t)(n_utt + 1) * sizeof(PreUttDev));
+    for (int u = 0; u < n_utt; ++u) {
+        if (utts[u].n_frames < 1) return 0;
+        total += pre_many_slice(p, utts[u].n_frames, rows_only != 0, nullptr);
+    }
+    return total;
+}
+
+extern "C" int wrnn_pre_upsample_many(const wrnn_pre *p, const wrnn_pre_utt *utts, int32_t n_utt, int32_t rows_only, float *mels_up, float *aux,
+                                      void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!p || !mels_up || !aux || !workspace) PRE_FAIL(WRNN_ERR_ARG, "NULL argument");
+    if (!utts) PRE_FAIL(WRNN_ERR_ARG, "NULL utterance table");
+    if (n_utt < 1 || n_utt > 65536) PRE_FAIL(WRNN_ERR_ARG, "bad utterance count %d (1 .. 65536 per call)", n_utt);
+    for (int u = 0; u < n_utt; ++u) {
+        if (utts[u].n_frames < 1 || (double)utts[u].n_frames * p->total_scale > 2.0e9) PRE_FAIL(WRNN_ERR_ARG, "utterance %d: bad n_frames %d", u, utts[u].n_frames);
+        if (!utts[u].mel || utts[u].up_row < 0 || utts[u].aux_row < 0) PRE_FAIL(WRNN_ERR_ARG, "utterance %d: NULL mel or negative output offset", u);
+    }
+    const size_t need = wrnn_pre_workspace_bytes_many(p, utts, n_utt, rows_only);
+    if (workspace_bytes < need) PRE_FAIL(WRNN_ERR_ARG, "workspace too small: %zu bytes, wrnn_pre_workspace_bytes_many says %zu", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) PRE_FAIL(WRNN_ERR_ARG, "workspace must be 256-byte aligned");
+    if (p->device < 0) PRE_FAIL(WRNN_ERR_NO_DEVICE, "a dims-only handle (wrnn_pre_debug_host_handle) launches nothing");
+    const bool rows = rows_only != 0;
+    char *ws = (char *)workspace;
+    size_t off = al256((size_t)(n_utt + 1) * sizeof(PreUttDev));
+    if (!pre_many_batched(p)) {                                  // other hparams: the per-utterance path, one workspace slice each
+        for (int u = 0; u < n_utt; ++u) {
+            const size_t slice = pre_many_slice(p, utts[u].n_frames, rows, nullptr);
+            const int rc = pre_run(p, utts[u].mel, utts[u].n_frames, mels_up + (size_t)utts[u].up_row * p->feat, aux + (size_t)utts[u].aux_row * p->R,
+                                   ws + off, slice, stream_, rows);
+            if (rc != WRNN_OK) return rc;
+            off += slice;
+        }
+        return WRNN_OK;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    DeviceGuard dg(p->device);
+    PRE_HIP(dg.err);
+    // the table: per utterance its pointers and the first block it owns in each stage's grid -- the grids an utterance gets are those of
+    // wrnn_pre_upsample (pre_run), so a tile is the same tile
+    auto grid = [](long total) { long b = (total + 255) / 256; return (long)(b > 65535 ? 65535 : (b < 1 ? 1 : b)); };
+    std::vector<PreUttDev> tab((size_t)n_utt + 1);
+    long blk[4] = {0, 0, 0, 0};
+    for (int u = 0; u < n_utt; ++u) {
+        const int n = utts[u].n_frames;
+        const long nf = (long)n + 2 * PPAD;
+        size_t s2_off = 0;
+        const size_t slice = pre_many_slice(p, n, rows, &s2_off);
+        PreUttDev &d = tab[u];
+        d.mel = utts[u].mel; d.up = mels_up + (size_t)utts[u].up_row * PFEAT; d.aux = aux + (size_t)utts[u].aux_row * PC;
+        d.s1 = (float *)(ws + off); d.s2 = rows ? nullptr : (float *)(ws + off + s2_off);
+        d.n = n; d.pad_ = 0;
+        for (int s = 0; s < 4; ++s) d.blk[s] = (int)blk[s];
+        blk[0] += (n + PNF - 1) / PNF;
+        blk[1] += grid(nf * 5 * PFEAT);
+        blk[2] += grid(nf * 25 * PFEAT);
+        blk[3] += rows ? 0 : grid((long)n * p->total_scale * 4);
+        for (int s = 0; s < 4; ++s)
+            if (blk[s] > 0x7fffffffL) PRE_FAIL(WRNN_ERR_ARG, "too many frames for one call (stage grid of %ld workgroups); split the table", blk[s]);
+        off += slice;
+    }
+    memset(&tab[n_utt], 0, sizeof(PreUttDev));
+    for (int s = 0; s < 4; ++s) tab[n_utt].blk[s] = (int)blk[s];
+    PreUttDev *d_tab = (PreUttDev *)ws;
+    // (pageable source: the runtime stages it before returning, as for the segment tables of wrnn_generate_segments)
+    PRE_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(PreUttDev), hipMemcpyHostToDevice, stream));
+    PreManyArgs m;
+    memset(&m, 0, sizeof m);
+    m.w.conv_in_w = p->conv_in_w; m.w.bn_in = p->bn_in; m.w.res_w = p->res_w; m.w.res_bn = p->res_bn;
+    m.w.conv_out_w = p->conv_out_w; m.w.conv_out_b = p->conv_out_b; m.w.blocks = p->blocks;
+    m.utt = d_tab; m.n_utt = n_utt;
+    hipLaunchKernelGGL(wrnn_resnet_many_kernel, dim3((unsigned)blk[0]), dim3(256), 0, stream, m);
+    hipLaunchKernelGGL((wrnn_upstage_many_kernel<true, false, 5>), dim3((unsigned)blk[1]), dim3(256), 0, stream, d_tab, n_utt, p->taps[0]);
+    if (rows) {
+        hipLaunchKernelGGL((wrnn_upstage_many_kernel<false, true, 5>), dim3((unsigned)blk[2]), dim3(256), 0, stream, d_tab, n_utt, p->taps[1]);
+    } else {
+        hipLaunchKernelGGL((wrnn_upstage_many_kernel<false, false, 5>), dim3((unsigned)blk[2]), dim3(256), 0, stream, d_tab, n_utt, p->taps[1]);
+        hipLaunchKernelGGL((wrnn_upstage_last_many_kernel<11>), dim3((unsigned)blk[3]), dim3(256), 0, stream, d_tab, n_utt, p->taps[2], PPAD * p->total_scale);
+    }
+    PRE_HIP(hipGetLastError());
+    return WRNN_OK;
 }

@@ -146,10 +146,19 @@ class WaveRNN(nn.Module):
         #: 'native' = the HIP pre-loop kernels (MFMA MelResNet + box-filter up-sampling, wrnn_pre_*);
         #: 'torch' = the nn.Modules below through PyTorch-ROCm (MIOpen)
         self.pre_algo = 'native'
-        #: generate_corpus: the pre-loop kernels of a chunk's utterances run side by side on this many side streams (1 = one after the other on the
-        #: current stream); the finished float64 audio comes back through page-locked memory (False: a pageable copy)
+        #: generate_corpus: True (default) = the pre-loop stages of ALL of a chunk's utterances in one launch each (`wrnn_pre_upsample_many`).  False (A/B) =
+        #: utterance by utterance: side by side on `pre_streams` side streams (1 = one after the other on the current stream).  The same bits every way.
+        #: The finished float64 audio comes back through page-locked memory (`pinned_output`; False: a pageable copy)
+        self.pre_batched = True
         self.pre_streams = 8
         self.pinned_output = True
+        #: generate_corpus: the post-loop stage's tables (first / folds / offsets, fades, mu-law table) are put on the device BEFORE the loop is queued --
+        #: they depend on the plan only -- so that behind the last loop launch there is one unfold launch and one copy into the pinned buffer, no host
+        #: round trip.  False = uploaded where they are used, behind the loop (A/B; the same audio)
+        self.post_tables_early = True
+        #: True = the slab's derived noise, aux tables and placement words prepared by three calls instead of wrnn_slab_prep_kernel
+        #: (wrnn_options.tuning bit 13; A/B, the same samples)
+        self.slab_prep_split = False
         #: True = when the call runs on wrnn_duo_kernel / wrnn_chain_kernel / wrnn_sparse_kernel (and the pre-loop stage is 'native' with a last stretch
         #: factor of 11), the LAST up-sampling stage and the crop are formed inside the loop from that stage's input (`engine.MelRows`): the [L, feat]
         #: up-sampled mel is never written -- 29 B of conditioning per audio sample resident instead of 320 B (a 64-utterance corpus:

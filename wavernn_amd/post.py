@@ -37,27 +37,54 @@ def _mu_law_lut(n_classes, device):
     return _tables[key]
 
 
-def unfold_on_device(segments, first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched=True):
+class UnfoldTables:
+    """Everything `wrnn_post_unfold` reads besides the segments, on the device: it depends on the plan only (which utterance owns which segments, the
+    wave lengths, overlap / hop / classes), so `prepare_unfold` can put it there BEFORE the loop is queued -- one copy from a page-locked staging array
+    (offsets int64, then first / folds int32), the cached fade and mu-law tables, the output buffer.  Nothing then lies between the last loop launch and
+    the unfold launch but the launch itself."""
+
+    def __init__(self, first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched, dev):
+        self.tail_len = 20 * hop
+        if min(wave_lens) < self.tail_len:
+            raise ValueError(f'operands could not be broadcast together with shapes ({min(wave_lens)},) ({self.tail_len},)')
+        n = self.n_utt = len(wave_lens)
+        self.off = np.concatenate([[0], np.cumsum(wave_lens)]).astype(np.int64)
+        stage = torch.empty(8 * (n + 1) + 8 * n, dtype=torch.uint8, pin_memory=True)
+        h = stage.numpy()
+        h[:8 * (n + 1)] = self.off.view(np.uint8)
+        h[8 * (n + 1):] = np.concatenate([np.asarray(first, np.int32), np.asarray(folds, np.int32)]).view(np.uint8)
+        self.tabs = stage.to(dev, non_blocking=True)         # (the caching host allocator keeps the pages until the copy has run)
+        self.overlap, self.batched, self.n_classes = (overlap if batched else 0), bool(batched), n_classes
+        self.fade_in, self.fade_out, self.tail = _fade_tables(self.overlap, hop, dev)
+        self.lut = _mu_law_lut(n_classes, dev) if mu_law else None
+        self.out = torch.empty(int(self.off[-1]), dtype=torch.float64, device=dev)
+        self.key = (tuple(int(x) for x in first), tuple(int(x) for x in folds), tuple(int(x) for x in wave_lens))
+
+
+def prepare_unfold(first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched=True, device='cuda'):
+    """The tables of `unfold_on_device(..., tables=...)` for these utterances, uploaded now, on the current stream."""
+    return UnfoldTables(first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched, torch.device(device))
+
+
+def unfold_on_device(segments, first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched=True, tables=None):
     """segments: float32 CUDA (n, T).  Utterance u owns rows [first[u], first[u]+folds[u]).  Returns a float64 CUDA tensor
     of all waveforms concatenated and the list of (start, end) slices.  Raises ValueError where the reference's tail
-    fade would (wave_len < 20*hop, :258)."""
+    fade would (wave_len < 20*hop, :258).  tables: what `prepare_unfold` made for the same utterances earlier (None: made here)."""
     dev = segments.device
-    tail_len = 20 * hop
-    if min(wave_lens) < tail_len:
-        raise ValueError(f'operands could not be broadcast together with shapes ({min(wave_lens)},) ({tail_len},)')
+    t = tables
+    if t is None:
+        t = UnfoldTables(first, folds, wave_lens, overlap, hop, n_classes, mu_law, batched, dev)
+    elif t.key != (tuple(int(x) for x in first), tuple(int(x) for x in folds), tuple(int(x) for x in wave_lens)) or t.lut is None and mu_law:
+        raise ValueError('unfold tables prepared for other utterances')
     L = _lib.lib()
-    n_utt, T = len(wave_lens), int(segments.shape[1])
-    off = np.concatenate([[0], np.cumsum(wave_lens)]).astype(np.int64)
-    tabs = torch.from_numpy(np.concatenate([np.asarray(first, np.int32), np.asarray(folds, np.int32)])).to(dev)
-    d_off = torch.from_numpy(off).to(dev)
-    fade_in, fade_out, tail = _fade_tables(overlap if batched else 0, hop, dev)
-    lut = _mu_law_lut(n_classes, dev) if mu_law else None
-    out = torch.empty(int(off[-1]), dtype=torch.float64, device=dev)
+    n_utt, T, off = t.n_utt, int(segments.shape[1]), t.off
     segments = segments.contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = L.wrnn_post_unfold(segments.data_ptr(), T, n_utt, tabs.data_ptr(), tabs.data_ptr() + 4 * n_utt, d_off.data_ptr(),
-                            lut.data_ptr() if lut is not None else None, n_classes, fade_in.data_ptr(), fade_out.data_ptr(),
-                            overlap if batched else 0, tail.data_ptr(), tail_len, 1 if batched else 0, out.data_ptr(), stream)
+    p_off = t.tabs.data_ptr()
+    p_first = p_off + 8 * (n_utt + 1)
+    rc = L.wrnn_post_unfold(segments.data_ptr(), T, n_utt, p_first, p_first + 4 * n_utt, p_off,
+                            t.lut.data_ptr() if t.lut is not None else None, n_classes, t.fade_in.data_ptr(), t.fade_out.data_ptr(),
+                            t.overlap, t.tail.data_ptr(), t.tail_len, 1 if t.batched else 0, t.out.data_ptr(), stream)
     if rc != 0:
         raise _lib.WrnnError(f'wrnn_post_unfold failed (rc={rc}): {L.wrnn_post_last_error().decode()}')
-    return out, [(int(off[u]), int(off[u + 1])) for u in range(n_utt)]
+    return t.out, [(int(off[u]), int(off[u + 1])) for u in range(n_utt)]

@@ -102,10 +102,39 @@ class PreEngine:
             raise _lib.WrnnError(f'wrnn_pre_upsample failed (rc={rc}): {self.lib.wrnn_pre_last_error().decode()}')
         return mels_up, aux
 
-    def upsample_many(self, jobs, rows=False, streams=8):
-        """jobs: [(mel, mels_up view, aux view)] -- the utterances of a chunk, each into its slice of the concatenated buffers.  An utterance's three
-        kernels fill 41 of the 256 CUs (641 frames) and depend on each other; the utterances do not: they run side by side on up to `streams` side
-        streams (own workspace each), forked from and joined to the current stream by events.  streams <= 1: one after the other on the current stream."""
+    def upsample_batched(self, jobs, rows=False):
+        """`wrnn_pre_upsample_many`: every stage of ALL the jobs' utterances in one launch on the current stream (one library call, one table upload);
+        bitwise what `upsample` / `upsample_rows` write job by job.  The output views must be slices of two buffers (any order, not overlapping)."""
+        mels = [mel[0] if mel.dim() == 3 else mel for mel, _, _ in jobs]
+        mels = [m.to(self.device, torch.float32).contiguous() for m in mels]
+        tab = (_lib.PreUtt * len(jobs))()
+        up_base, aux_base = min(up.data_ptr() for _, up, _ in jobs), min(ax.data_ptr() for _, _, ax in jobs)
+        up_b, aux_b = 4 * self.feat_dims, 4 * self.res_out_dims
+        for k, (m, (_, up, ax)) in enumerate(zip(mels, jobs)):
+            n = int(m.shape[1])
+            if m.shape[0] != self.feat_dims:
+                raise ValueError(f'Expected a mel shaped ({self.feat_dims}, n_hops), but got {tuple(m.shape)}!')
+            assert up.is_contiguous() and ax.is_contiguous() and up.shape == ((self.rows_of(n) if rows else n * self.hop), self.feat_dims)
+            assert ax.shape == (n, self.res_out_dims) and (up.data_ptr() - up_base) % up_b == 0 and (ax.data_ptr() - aux_base) % aux_b == 0
+            tab[k].mel, tab[k].n_frames = m.data_ptr(), n
+            tab[k].up_row, tab[k].aux_row = (up.data_ptr() - up_base) // up_b, (ax.data_ptr() - aux_base) // aux_b
+        nbytes = int(self.lib.wrnn_pre_workspace_bytes_many(self._pre, tab, len(jobs), int(rows)))
+        ws = getattr(self, '_ws_many', None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws_many = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self.lib.wrnn_pre_upsample_many(self._pre, tab, len(jobs), int(rows), up_base, aux_base, ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            raise _lib.WrnnError(f'wrnn_pre_upsample_many failed (rc={rc}): {self.lib.wrnn_pre_last_error().decode()}')
+
+    def upsample_many(self, jobs, rows=False, streams=8, batched=True):
+        """jobs: [(mel, mels_up view, aux view)] -- the utterances of a chunk, each into its slice of the concatenated buffers.  batched (default):
+        `upsample_batched`, one launch per stage for all of them.  batched=False, the per-utterance paths, stays for A/B (`model.pre_batched`,
+        `model.pre_streams`): an utterance's kernels fill 41 of the 256 CUs (641 frames) and depend on each other; the utterances do not: they run side by side
+        on up to `streams` side streams (own workspace each), forked from and joined to the current stream by events; streams <= 1: one after the other on
+        the current stream."""
+        if batched and jobs:
+            return self.upsample_batched(jobs, rows=rows)
         if streams <= 1 or len(jobs) <= 1:
             for mel, up, aux in jobs:
                 self.upsample(mel, mels_up=up, aux=aux, _rows=rows)
