@@ -496,6 +496,23 @@ typedef struct wrnn_bigru_call {
     void *stream;
 } wrnn_bigru_call;
 int wrnn_bigru(int device, const wrnn_bigru_call *c);
+/* The same GRU for n_seq sequences that share one weight set, in ONE launch of (2, n_seq) workgroups (appended to ABI v9: the symbol tells whether
+ * a library has it): sequence s owns rows [off_s, off_s + T[s]) of gi_fwd / gi_rev / out, off = the prefix sum of T; workgroup (direction, s)
+ * runs the loop of wrnn_bigru on those rows, so out is bit-identical to n_seq wrnn_bigru calls.  No workgroup waits for another (not a
+ * cooperative launch).  WRNN_ERR_ARG for a struct size mismatch, n_seq outside 1..WRNN_TACO_FRONT_MANY_MAX, a T[s] outside 1..2^20, or a NULL
+ * buffer.  T is read during the call only. */
+#define WRNN_TACO_FRONT_MANY_MAX 64
+typedef struct wrnn_bigru_many_call {
+    uint32_t struct_bytes;
+    int32_t n_seq, hidden;                   /* 1..WRNN_TACO_FRONT_MANY_MAX; 128 */
+    const int32_t *T;                        /* HOST [n_seq]: frames per sequence */
+    const float *gi_fwd, *gi_rev;            /* [sum T][3 hidden], sequence after sequence */
+    const float *w_hh_fwd, *w_hh_rev;        /* [3 hidden][hidden] */
+    const float *b_hh_fwd, *b_hh_rev;        /* [3 hidden] */
+    float *out;                              /* [sum T][2 hidden] */
+    void *stream;
+} wrnn_bigru_many_call;
+int wrnn_bigru_many(int device, const wrnn_bigru_many_call *c);
 
 /*
  * The rest of Tacotron inference around the decoder loop (csrc/wrnn_cbhg.hip): the embedding and the encoder pre-net, both CBHGs (reference
@@ -551,6 +568,30 @@ int wrnn_taco_encode(const wrnn_taco_front *f, const int32_t *ids, int32_t n, fl
  * (the reference returns its transpose; the vocoder takes it).  pre_rnn_out as above, [N][channels]. */
 int wrnn_taco_postnet(const wrnn_taco_front *f, const float *mel, int32_t N, float *linear_out, float *pre_rnn_out,
                       void *workspace, size_t workspace_bytes, void *stream);
+/* Both for a LIST of 1..WRNN_TACO_FRONT_MANY_MAX sentences in one call (appended to ABI v9: the symbols tell whether a library has them).  Sentence s
+ * owns rows [off_s, off_s + n_s) of every concatenated tensor -- ids, seq_out, seq_proj_out, linear_out, pre_rnn_out -- where off is the prefix sum of
+ * the lengths; every row width the library supports is a multiple of 16 floats, so a sentence's slice is 16-byte aligned when the tensor is, and a
+ * slice of seq_out / seq_proj_out is directly what wrnn_taco_batch_call.seq[s] / seq_proj[s] take.  Every stage is ONE launch for all sentences
+ * (wrnn_*_many_kernel: a workgroup finds its sentence and its tile in a small table passed with the launch; the GRU runs as wrnn_bigru_many); tiles,
+ * conv windows, the max-pool's padding and the residual are taken per sentence, so every output element sees the operands of the single-sentence call
+ * in the same order: the outputs of sentence s are BIT-IDENTICAL to wrnn_taco_encode / wrnn_taco_postnet on that sentence alone, whatever rides along
+ * and in whatever order, and rows outside a sentence's range are not touched.  Asynchronous on `stream`; no allocation, no synchronisation; `n`, `N`
+ * and `mel` are read during the call only.  WRNN_ERR_ARG (the message names the sentence and the limit), before anything is launched, for a NULL
+ * handle, table or output, n_sent outside 1..WRNN_TACO_FRONT_MANY_MAX, a length outside 1..2^20, a NULL mel[s], an output that is not 16-byte or a
+ * workspace that is not 256-byte aligned; WRNN_ERR_WORKSPACE below wrnn_taco_front_workspace_bytes_many (which is 0 for a bad table). */
+size_t wrnn_taco_front_workspace_bytes_many(const wrnn_taco_front *f, const int32_t *n, int32_t n_sent);
+int wrnn_taco_encode_many(const wrnn_taco_front *f, const int32_t *ids /* DEVICE [sum n], sentence after sentence */,
+                          const int32_t *n /* HOST [n_sent] */, int32_t n_sent,
+                          float *seq_out /* DEVICE [sum n][2 channels] */, float *seq_proj_out /* DEVICE [sum n][encoder_proj_dims] */,
+                          float *pre_rnn_out /* NULL or DEVICE [sum n][channels] */,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int wrnn_taco_postnet_many(const wrnn_taco_front *f, const float *const *mel /* HOST [n_sent] of DEVICE [n_mels][N_s] */,
+                           const int32_t *N /* HOST [n_sent] */, int32_t n_sent,
+                           float *linear_out /* DEVICE [sum N][fft_bins] */, float *pre_rnn_out /* NULL or DEVICE [sum N][channels] */,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook: a handle holding the DIMS of `w` only (no device, no weights; no weight pointer of `w` is read): the size queries answer on it, and
+ * every entry point that would launch returns WRNN_ERR_NO_DEVICE on it BEHIND its argument checks.  wrnn_taco_front_destroy frees it. */
+int wrnn_taco_front_debug_host_handle(const wrnn_taco_front_weights *w, wrnn_taco_front **out);
 
 /* Self tests of the device primitives (MFMA fragment layout, inter-workgroup granule all-gather).
  * Synchronous.  WRNN_OK or an error with a message. */

@@ -29,7 +29,9 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_pre_upsample_many', 'wrnn_pre_debug_host_handle', 'wrnn_pre_last_error',
            'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
-           'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch']
+           'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch',
+           'wrnn_bigru_many', 'wrnn_taco_front_workspace_bytes_many', 'wrnn_taco_encode_many', 'wrnn_taco_postnet_many',
+           'wrnn_taco_front_debug_host_handle']
 
 
 class Weights(ctypes.Structure):
@@ -87,6 +89,15 @@ class TacoBatchCall(ctypes.Structure):
 class BigruCall(ctypes.Structure):
     """wrnn_bigru_call."""
     _fields_ = [('struct_bytes', ctypes.c_uint32), ('T', ctypes.c_int32), ('hidden', ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ('gi_fwd', 'gi_rev', 'w_hh_fwd', 'w_hh_rev', 'b_hh_fwd', 'b_hh_rev', 'out', 'stream')]
+
+
+TACO_FRONT_MANY_MAX = 64     # WRNN_TACO_FRONT_MANY_MAX: sentences per wrnn_taco_encode_many / wrnn_taco_postnet_many / wrnn_bigru_many call
+
+
+class BigruManyCall(ctypes.Structure):
+    """wrnn_bigru_many_call: T points to a HOST array of n_seq lengths; gi_* / out hold the sequences one after another."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('n_seq', ctypes.c_int32), ('hidden', ctypes.c_int32), ('T', ctypes.POINTER(ctypes.c_int32))] + \
                [(n, ctypes.c_void_p) for n in ('gi_fwd', 'gi_rev', 'w_hh_fwd', 'w_hh_rev', 'b_hh_fwd', 'b_hh_rev', 'out', 'stream')]
 
 
@@ -258,6 +269,14 @@ def lib():
                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     L.wrnn_taco_postnet.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p]
+    L.wrnn_bigru_many.argtypes = [ctypes.c_int, ctypes.POINTER(BigruManyCall)]
+    L.wrnn_taco_front_workspace_bytes_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
+    L.wrnn_taco_front_workspace_bytes_many.restype = ctypes.c_size_t
+    L.wrnn_taco_encode_many.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.wrnn_taco_postnet_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.wrnn_taco_front_debug_host_handle.argtypes = [ctypes.POINTER(TacoFrontWeights), ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.wrnn_selftest.argtypes = [ctypes.c_int, ctypes.c_int]
     L.wrnn_selftest_metric.restype = ctypes.c_float

@@ -1,7 +1,9 @@
 // wrnn_cbhg.hip -- Tacotron's encoder and post-net on MI355X (gfx950) around the two persistent kernels of wrnn_taco.hip: the embedding
 // and the encoder pre-net (reference models/tacotron.py:24-39, :141-155), both CBHGs in front of their GRU (:57-139: conv bank of
 // BatchNormConv :43-54, max-pool, two projections, residual, pre_highway, highways, the two W_ih products), `encoder_proj` and
-// `post_proj` (:403-404, :424-425).  Once per sentence; ordinary data-parallel kernels, no cooperative launch, no inter-workgroup wait.
+// `post_proj` (:403-404, :424-425).  Once per sentence (wrnn_taco_encode / wrnn_taco_postnet), or once for a LIST of sentences
+// (wrnn_taco_encode_many / wrnn_taco_postnet_many: K-cbhg-many below); ordinary data-parallel kernels, no cooperative launch, no
+// inter-workgroup wait.
 // All arithmetic is float32 on v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulation); activations travel as
 // [position][channel] rows.
 //
@@ -21,7 +23,14 @@
 //           pre_highway, gi = W_ih x + b_ih of both directions, encoder_proj, post_proj.
 // K-cbhg-3  wrnn_highway_kernel: all highways (:7-21: x <- sigmoid(W2 x + b2) relu(W1 x + b1) + (1 - sigmoid(..)) x) of a 16-position
 //           tile in LDS, wave w owns channels [32w, 32w + 32) with the full K = 128 (no cross-wave sum); library expf, exact division.
-// The GRU itself is wrnn_bigru (wrnn_taco.hip), called from here.
+// K-cbhg-many  wrnn_cbhg_bank_many_kernel / wrnn_cbhg_conv_many_kernel / wrnn_rowlin_many_kernel / wrnn_highway_many_kernel: the same tile
+//           bodies for up to 64 sentences in one launch.  The sentences' rows lie one after another in every [position][channel] tensor;
+//           a sentence table (lengths, first rows, first tiles, the post-net's per-sentence input pointers) is a kernel argument;
+//           blockIdx.x runs over the concatenated tile list, the workgroup finds (sentence, tile in sentence), rebases a private copy of
+//           the arguments to the sentence and calls the body with the sentence-relative position -- tiles restart at position 0 of every
+//           sentence, so windows, the pool's and the conv's padding and the residual never see a neighbour's rows and every output
+//           element has the operands and the summation order of the single-sentence launch: bitwise the same result.
+// The GRU itself is wrnn_bigru / wrnn_bigru_many (wrnn_taco.hip), called from here.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -157,6 +166,69 @@ __global__ __launch_bounds__(NT) void wrnn_cbhg_bank_kernel(const ConvArgs b)
     cb_conv_tile(a, blockIdx.x * CB_NP, blockIdx.y * 16);
 }
 
+// Several sentences in one launch (wrnn_taco_encode_many / wrnn_taco_postnet_many).  The sentence table travels with the launch as a kernel argument:
+// sentence s has n[s] positions, owns rows [row0[s], row0[s] + n[s]) of every concatenated [row][channel] tensor and tiles [tile0[s], tile0[s + 1]) of
+// the grid's x; src[s] is its own [n_mels][N_s] tensor (the post-net's input and residual).
+constexpr int CB_MANY = WRNN_TACO_FRONT_MANY_MAX;
+struct FrontTab {
+    int n_sent;
+    int n[CB_MANY], row0[CB_MANY], tile0[CB_MANY + 1];
+    const float *src[CB_MANY];
+};
+
+// the sentence that owns tile `b` of the concatenated tile list (tile0 is increasing: every sentence has at least one tile)
+__device__ __forceinline__ int cb_sentence_of(const FrontTab &t, int b)
+{
+    int lo = 0, hi = t.n_sent;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t.tile0[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the arguments of the single-sentence launch on sentence s: tiles, windows, the pool's and the conv's padding and the residual are then relative to
+// the sentence, and no load or store leaves its rows
+__device__ __forceinline__ ConvArgs cb_rebase(const ConvArgs &b, const FrontTab &t, int s)
+{
+    ConvArgs a = b;
+    const size_t r0 = (size_t)t.row0[s];
+    a.n = t.n[s];
+    if (b.flags & CB_IN_CMAJOR) a.in = t.src[s];
+    else if (b.ids) a.ids = b.ids + r0;                                     // (`in` is the table the ids index)
+    else a.in = b.in + r0 * b.ldin;
+    if (b.res) a.res = (b.flags & CB_RES_CMAJOR) ? t.src[s] : b.res + r0 * b.ldres;
+    a.out = b.out + r0 * b.ldo;
+    return a;
+}
+
+__global__ __launch_bounds__(NT) void wrnn_cbhg_conv_many_kernel(const ConvArgs b, const FrontTab t)
+{
+    const int s = cb_sentence_of(t, blockIdx.x);
+    const ConvArgs a = cb_rebase(b, t, s);
+    cb_conv_tile(a, (blockIdx.x - t.tile0[s]) * CB_NP, blockIdx.y * 16);
+}
+
+__global__ __launch_bounds__(NT) void wrnn_rowlin_many_kernel(const ConvArgs b, const FrontTab t)
+{
+    const int s = cb_sentence_of(t, blockIdx.x);
+    const ConvArgs a = cb_rebase(b, t, s);
+    cb_conv_tile(a, (blockIdx.x - t.tile0[s]) * CB_NP, blockIdx.y * 16);
+}
+
+__global__ __launch_bounds__(NT) void wrnn_cbhg_bank_many_kernel(const ConvArgs b, const FrontTab t)
+{
+    const int s = cb_sentence_of(t, blockIdx.x);
+    ConvArgs a = cb_rebase(b, t, s);
+    const int z = blockIdx.z;                                               // as wrnn_cbhg_bank_kernel
+    a.taps = z + 1;
+    a.w = b.w + (size_t)CB_C * b.Cin * (z * (z + 1) / 2);
+    a.scale = b.scale + (size_t)z * 2 * CB_C;
+    a.shift = a.scale + CB_C;
+    a.out += (size_t)z * CB_C;
+    cb_conv_tile(a, (blockIdx.x - t.tile0[s]) * CB_NP, blockIdx.y * 16);
+}
+
 struct HighwayArgs {
     const float *in;            // [n][128]
     float *out;                 // [n][128] (may be `in`: a workgroup reads and writes its own rows only)
@@ -171,12 +243,13 @@ __device__ __forceinline__ f32x4 cb_tile128(const float *W, int row0, const floa
     return mfma_tile(af, act + (lane & 15) * CB_LDX + 4 * (lane >> 4));
 }
 
-__global__ __launch_bounds__(NT) void wrnn_highway_kernel(const HighwayArgs a)
+// positions [p0, p0 + 16) through all highways
+__device__ __forceinline__ void cb_highway_tile(const HighwayArgs &a, int p0)
 {
     __shared__ __attribute__((aligned(16))) float XA[CB_NP * CB_LDX];
     __shared__ __attribute__((aligned(16))) float XB[CB_NP * CB_LDX];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int p0 = blockIdx.x * CB_NP, n = a.n;
+    const int n = a.n;
     for (int q = tid; q < CB_NP * (CB_C / 4); q += NT) {
         const int r = q / (CB_C / 4), c4 = (q % (CB_C / 4)) * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -212,6 +285,18 @@ __global__ __launch_bounds__(NT) void wrnn_highway_kernel(const HighwayArgs a)
         const int r = q / (CB_C / 4), c4 = (q % (CB_C / 4)) * 4;
         if (p0 + r < n) *reinterpret_cast<float4 *>(a.out + (size_t)(p0 + r) * CB_C + c4) = *reinterpret_cast<const float4 *>(cur + r * CB_LDX + c4);
     }
+}
+
+__global__ __launch_bounds__(NT) void wrnn_highway_kernel(const HighwayArgs a) { cb_highway_tile(a, blockIdx.x * CB_NP); }
+
+__global__ __launch_bounds__(NT) void wrnn_highway_many_kernel(const HighwayArgs b, const FrontTab t)
+{
+    const int s = cb_sentence_of(t, blockIdx.x);
+    HighwayArgs a = b;
+    a.in = b.in + (size_t)t.row0[s] * CB_C;
+    a.out = b.out + (size_t)t.row0[s] * CB_C;
+    a.n = t.n[s];
+    cb_highway_tile(a, (blockIdx.x - t.tile0[s]) * CB_NP);
 }
 
 }  // namespace wrnn
@@ -250,8 +335,8 @@ struct wrnn_taco_front {
 
 static bool cb_mult16(int v) { return v >= 16 && v <= 4096 && (v & 15) == 0; }
 
-// dims and pointers of one CBHG; `what` names it in the message.  Returns 0 or WRNN_ERR_ARG.
-static int cb_check(const wrnn_cbhg_weights *c, const char *what)
+// dims and (with `pointers`) pointers of one CBHG; `what` names it in the message.  Returns 0 or WRNN_ERR_ARG.
+static int cb_check(const wrnn_cbhg_weights *c, const char *what, bool pointers)
 {
     if (c->K < 1 || c->K > CB_MAXK) CB_FAIL(WRNN_ERR_ARG, "%s: conv bank of %d (1..%d)", what, c->K, CB_MAXK);
     if (c->channels != CB_C) CB_FAIL(WRNN_ERR_ARG, "%s: highway / GRU width %d (this build: %d, the width of wrnn_bigru)", what, c->channels, CB_C);
@@ -260,9 +345,10 @@ static int cb_check(const wrnn_cbhg_weights *c, const char *what)
                 c->proj1_channels, c->proj2_channels);
     if (c->proj2_channels != c->in_channels)
         CB_FAIL(WRNN_ERR_ARG, "%s: the residual needs conv_project2's %d channels to equal the input's %d", what, c->proj2_channels, c->in_channels);
-    if ((c->proj2_channels != CB_C) != (c->pre_highway_w != nullptr))
+    if (pointers && (c->proj2_channels != CB_C) != (c->pre_highway_w != nullptr))
         CB_FAIL(WRNN_ERR_ARG, "%s: pre_highway must be given exactly when conv_project2 has other than %d channels (%d)", what, CB_C, c->proj2_channels);
     if (c->num_highways < 0 || c->num_highways > CB_MAXHW) CB_FAIL(WRNN_ERR_ARG, "%s: %d highways (0..%d)", what, c->num_highways, CB_MAXHW);
+    if (!pointers) return WRNN_OK;
     bool ok = c->proj1_conv_w && c->proj1_bn_w && c->proj1_bn_b && c->proj1_bn_mean && c->proj1_bn_var && c->proj2_conv_w && c->proj2_bn_w &&
               c->proj2_bn_b && c->proj2_bn_mean && c->proj2_bn_var && c->rnn_w_ih && c->rnn_w_hh && c->rnn_b_ih && c->rnn_b_hh && c->rnn_w_ih_rev &&
               c->rnn_w_hh_rev && c->rnn_b_ih_rev && c->rnn_b_hh_rev;
@@ -272,7 +358,7 @@ static int cb_check(const wrnn_cbhg_weights *c, const char *what)
     return WRNN_OK;
 }
 
-extern "C" int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int device, wrnn_taco_front **out)
+static int cb_check_front(const wrnn_taco_front_weights *w, wrnn_taco_front **out, bool pointers)
 {
     if (!w || !out) CB_FAIL(WRNN_ERR_ARG, "NULL argument");
     if (w->struct_bytes != sizeof(wrnn_taco_front_weights)) CB_FAIL(WRNN_ERR_ARG, "struct size mismatch (header / library versions differ)");
@@ -280,14 +366,47 @@ extern "C" int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int devi
         !cb_mult16(w->n_mels) || !cb_mult16(w->fft_bins))
         CB_FAIL(WRNN_ERR_ARG, "bad dims: %d symbols; embedding %d, pre-net %d / %d, encoder_proj %d, n_mels %d, fft_bins %d must be multiples of 16 in 16..4096",
                 w->n_symbols, w->embed_dims, w->prenet1, w->prenet2, w->encoder_proj_dims, w->n_mels, w->fft_bins);
-    if (!w->embedding || !w->prenet_fc1_w || !w->prenet_fc1_b || !w->prenet_fc2_w || !w->prenet_fc2_b || !w->encoder_proj_w || !w->post_proj_w)
+    if (pointers && (!w->embedding || !w->prenet_fc1_w || !w->prenet_fc1_b || !w->prenet_fc2_w || !w->prenet_fc2_b || !w->encoder_proj_w || !w->post_proj_w))
         CB_FAIL(WRNN_ERR_ARG, "NULL weight pointer");
-    int rc = cb_check(&w->encoder_cbhg, "encoder.cbhg");
-    if (rc == WRNN_OK) rc = cb_check(&w->postnet, "postnet");
+    int rc = cb_check(&w->encoder_cbhg, "encoder.cbhg", pointers);
+    if (rc == WRNN_OK) rc = cb_check(&w->postnet, "postnet", pointers);
     if (rc != WRNN_OK) return rc;
     if (w->encoder_cbhg.in_channels != w->prenet2)
         CB_FAIL(WRNN_ERR_ARG, "encoder.cbhg takes %d channels, the pre-net gives %d", w->encoder_cbhg.in_channels, w->prenet2);
     if (w->postnet.in_channels != w->n_mels) CB_FAIL(WRNN_ERR_ARG, "postnet takes %d channels, n_mels is %d", w->postnet.in_channels, w->n_mels);
+    return WRNN_OK;
+}
+
+// the dims of `w` and the workspace row widths that follow from them
+static void cb_set_dims(wrnn_taco_front *f, const wrnn_taco_front_weights *w, int device)
+{
+    f->device = device;
+    f->n_symbols = w->n_symbols; f->E = w->embed_dims; f->PN1 = w->prenet1; f->D = w->encoder_proj_dims; f->n_mels = w->n_mels; f->fft = w->fft_bins;
+    const wrnn_cbhg_weights *c[2] = {&w->encoder_cbhg, &w->postnet};
+    CbhgDev *d[2] = {&f->enc, &f->post};
+    for (int i = 0; i < 2; ++i) { d[i]->K = c[i]->K; d[i]->Cin = c[i]->in_channels; d[i]->P1 = c[i]->proj1_channels; d[i]->P2 = c[i]->proj2_channels; d[i]->layers = c[i]->num_highways; }
+    auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
+    f->w_t0 = mx((size_t)f->PN1, mx((size_t)f->enc.P1, (size_t)f->post.P1));
+    f->w_x = mx((size_t)f->enc.Cin, (size_t)f->post.Cin);
+    f->w_bank = (size_t)CB_C * mx((size_t)f->enc.K, (size_t)f->post.K);
+}
+
+// Test hook: a handle that holds the DIMS of `w` and nothing else (device -1, no weights; no weight pointer of `w` is read).  The size queries answer on
+// it; every entry point that would launch fails on it with WRNN_ERR_NO_DEVICE -- behind its argument checks, which is what the handle is for.
+extern "C" int wrnn_taco_front_debug_host_handle(const wrnn_taco_front_weights *w, wrnn_taco_front **out)
+{
+    const int rc = cb_check_front(w, out, false);
+    if (rc != WRNN_OK) return rc;
+    wrnn_taco_front *f = new wrnn_taco_front();
+    cb_set_dims(f, w, -1);
+    *out = f;
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int device, wrnn_taco_front **out)
+{
+    const int rc = cb_check_front(w, out, true);
+    if (rc != WRNN_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
         CB_FAIL(WRNN_ERR_NO_DEVICE, "no HIP device %d (count %d)", device, ndev);
@@ -365,22 +484,16 @@ extern "C" int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int devi
     if (e != hipSuccess) { delete f; CB_FAIL(WRNN_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
     e = hipMemcpy(f->dev, h.data(), h.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(f->dev); delete f; CB_FAIL(WRNN_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e)); }
-    f->device = device;
-    f->n_symbols = w->n_symbols; f->E = w->embed_dims; f->PN1 = w->prenet1; f->D = w->encoder_proj_dims; f->n_mels = w->n_mels; f->fft = w->fft_bins;
+    cb_set_dims(f, w, device);
     f->emb = f->dev + o_emb; f->fc1_w = f->dev + o_f1w; f->fc1_b = f->dev + o_f1b; f->fc2_w = f->dev + o_f2w; f->fc2_b = f->dev + o_f2b;
     f->enc_proj_w = f->dev + o_ep; f->post_proj_w = f->dev + o_pp;
     auto fill = [&](CbhgDev &d, const wrnn_cbhg_weights &c, const Off &o) {
-        d.K = c.K; d.Cin = c.in_channels; d.P1 = c.proj1_channels; d.P2 = c.proj2_channels; d.layers = c.num_highways;
         d.bank_w = f->dev + o.bank_w; d.bank_ss = f->dev + o.bank_ss; d.p1_w = f->dev + o.p1_w; d.p1_ss = f->dev + o.p1_ss;
         d.p2_w = f->dev + o.p2_w; d.p2_ss = f->dev + o.p2_ss; d.pre_hw_w = c.pre_highway_w ? f->dev + o.pre_hw : nullptr; d.hw = f->dev + o.hw;
         for (int i = 0; i < 2; ++i) { d.w_ih[i] = f->dev + o.w_ih[i]; d.b_ih[i] = f->dev + o.b_ih[i]; d.w_hh[i] = f->dev + o.w_hh[i]; d.b_hh[i] = f->dev + o.b_hh[i]; }
     };
     fill(f->enc, w->encoder_cbhg, oe);
     fill(f->post, w->postnet, op);
-    auto mx = [](size_t a, size_t b) { return a > b ? a : b; };
-    f->w_t0 = mx((size_t)f->PN1, mx((size_t)f->enc.P1, (size_t)f->post.P1));
-    f->w_x = mx((size_t)f->enc.Cin, (size_t)f->post.Cin);
-    f->w_bank = (size_t)CB_C * mx((size_t)f->enc.K, (size_t)f->post.K);
     *out = f;
     return WRNN_OK;
 }
@@ -388,7 +501,7 @@ extern "C" int wrnn_taco_front_create(const wrnn_taco_front_weights *w, int devi
 extern "C" void wrnn_taco_front_destroy(wrnn_taco_front *f)
 {
     if (!f) return;
-    (void)hipFree(f->dev);
+    if (f->dev) (void)hipFree(f->dev);
     delete f;
 }
 
@@ -431,38 +544,67 @@ static ConvArgs cb_linear(const float *in, int ldin, const float *w, const float
     return a;
 }
 
-// One CBHG: x ([n][Cin] rows, or [Cin][n] with x_cmajor) -> gru_out [n][256]; pre_rnn (optional) receives the highway output
-static int cb_run_cbhg(const wrnn_taco_front *f, const CbhgDev &d, const float *x, bool x_cmajor, int n, const CbWs &s, float *gru_out,
-                       float *pre_rnn, hipStream_t stream)
+enum CbKernel { CB_K_CONV, CB_K_ROWLIN, CB_K_BANK };
+
+// One stage on a grid of (position tiles, gy, gz): the single-sentence kernel over a.n positions, or -- with a sentence table -- its _many twin over
+// the concatenated tile list (a.in / a.ids / a.res / a.out are then the concatenated tensors and a.n is unused)
+static void cb_launch(CbKernel k, const ConvArgs &a, unsigned gy, unsigned gz, const FrontTab *tab, hipStream_t stream)
 {
-    const unsigned tiles = (unsigned)((n + CB_NP - 1) / CB_NP);
+    if (tab) {
+        const dim3 grid((unsigned)tab->tile0[tab->n_sent], gy, gz);
+        if (k == CB_K_BANK) hipLaunchKernelGGL(wrnn_cbhg_bank_many_kernel, grid, dim3(NT), 0, stream, a, *tab);
+        else if (k == CB_K_CONV) hipLaunchKernelGGL(wrnn_cbhg_conv_many_kernel, grid, dim3(NT), 0, stream, a, *tab);
+        else hipLaunchKernelGGL(wrnn_rowlin_many_kernel, grid, dim3(NT), 0, stream, a, *tab);
+        return;
+    }
+    const dim3 grid((unsigned)((a.n + CB_NP - 1) / CB_NP), gy, gz);
+    if (k == CB_K_BANK) hipLaunchKernelGGL(wrnn_cbhg_bank_kernel, grid, dim3(NT), 0, stream, a);
+    else if (k == CB_K_CONV) hipLaunchKernelGGL(wrnn_cbhg_conv_kernel, grid, dim3(NT), 0, stream, a);
+    else hipLaunchKernelGGL(wrnn_rowlin_kernel, grid, dim3(NT), 0, stream, a);
+}
+
+// One CBHG: x ([n][Cin] rows, or [Cin][n] with x_cmajor) -> gru_out [n][256]; pre_rnn (optional) receives the highway output.  With a sentence
+// table n is the sum of the lengths, the row tensors are the concatenated ones and a [Cin][n_s] input is taken from the table's src[s].
+static int cb_run_cbhg(const wrnn_taco_front *f, const CbhgDev &d, const float *x, bool x_cmajor, int n, const FrontTab *tab, const CbWs &s,
+                       float *gru_out, float *pre_rnn, hipStream_t stream)
+{
     ConvArgs a;
     memset(&a, 0, sizeof a);                                                // the bank: ReLU -> BatchNorm, all widths in one launch
     a.in = x; a.w = d.bank_w; a.scale = d.bank_ss; a.out = s.bank;
     a.n = n; a.Cin = d.Cin; a.Cout = CB_C; a.ldin = d.Cin; a.ldo = d.K * CB_C; a.flags = CB_RELU | (x_cmajor ? CB_IN_CMAJOR : 0);
-    hipLaunchKernelGGL(wrnn_cbhg_bank_kernel, dim3(tiles, CB_C / 16, d.K), dim3(NT), 0, stream, a);
+    cb_launch(CB_K_BANK, a, CB_C / 16, d.K, tab, stream);
     memset(&a, 0, sizeof a);                                                // max-pool (in the loader) -> conv_project1 -> ReLU -> BatchNorm
     a.in = s.bank; a.w = d.p1_w; a.scale = d.p1_ss; a.shift = d.p1_ss + d.P1; a.out = s.t0;
     a.n = n; a.Cin = d.K * CB_C; a.Cout = d.P1; a.taps = 3; a.ldin = d.K * CB_C; a.ldo = d.P1; a.flags = CB_RELU | CB_POOL;
-    hipLaunchKernelGGL(wrnn_cbhg_conv_kernel, dim3(tiles, d.P1 / 16), dim3(NT), 0, stream, a);
+    cb_launch(CB_K_CONV, a, d.P1 / 16, 1, tab, stream);
     memset(&a, 0, sizeof a);                                                // conv_project2 -> BatchNorm -> + input
     a.in = s.t0; a.w = d.p2_w; a.scale = d.p2_ss; a.shift = d.p2_ss + d.P2; a.res = x; a.out = s.p2;
     a.n = n; a.Cin = d.P1; a.Cout = d.P2; a.taps = 3; a.ldin = d.P1; a.ldres = d.Cin; a.ldo = d.P2; a.flags = x_cmajor ? CB_RES_CMAJOR : 0;
-    hipLaunchKernelGGL(wrnn_cbhg_conv_kernel, dim3(tiles, d.P2 / 16), dim3(NT), 0, stream, a);
+    cb_launch(CB_K_CONV, a, d.P2 / 16, 1, tab, stream);
     const float *hin = s.p2;
     if (d.pre_hw_w) {
         a = cb_linear(s.p2, d.P2, d.pre_hw_w, nullptr, s.ph, n, d.P2, CB_C, 0);
-        hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3(tiles, CB_C / 16), dim3(NT), 0, stream, a);
+        cb_launch(CB_K_ROWLIN, a, CB_C / 16, 1, tab, stream);
         hin = s.ph;
     }
     HighwayArgs hgw;
     hgw.in = hin; hgw.out = pre_rnn ? pre_rnn : s.hw; hgw.hw = d.hw; hgw.n = n; hgw.layers = d.layers;
-    hipLaunchKernelGGL(wrnn_highway_kernel, dim3(tiles), dim3(NT), 0, stream, hgw);
+    if (tab) hipLaunchKernelGGL(wrnn_highway_many_kernel, dim3((unsigned)tab->tile0[tab->n_sent]), dim3(NT), 0, stream, hgw, *tab);
+    else hipLaunchKernelGGL(wrnn_highway_kernel, dim3((unsigned)((n + CB_NP - 1) / CB_NP)), dim3(NT), 0, stream, hgw);
     for (int dir = 0; dir < 2; ++dir) {
         a = cb_linear(hgw.out, CB_C, d.w_ih[dir], d.b_ih[dir], s.gi[dir], n, CB_C, 3 * CB_C, 0);
-        hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3(tiles, 3 * CB_C / 16), dim3(NT), 0, stream, a);
+        cb_launch(CB_K_ROWLIN, a, 3 * CB_C / 16, 1, tab, stream);
     }
     CB_HIP(hipGetLastError());
+    if (tab) {
+        wrnn_bigru_many_call g;
+        memset(&g, 0, sizeof g);
+        g.struct_bytes = sizeof g;
+        g.n_seq = tab->n_sent; g.hidden = CB_C; g.T = tab->n;
+        g.gi_fwd = s.gi[0]; g.gi_rev = s.gi[1]; g.w_hh_fwd = d.w_hh[0]; g.w_hh_rev = d.w_hh[1]; g.b_hh_fwd = d.b_hh[0]; g.b_hh_rev = d.b_hh[1];
+        g.out = gru_out; g.stream = (void *)stream;
+        return wrnn_bigru_many(f->device, &g);
+    }
     wrnn_bigru_call g;
     memset(&g, 0, sizeof g);
     g.struct_bytes = sizeof g;
@@ -477,6 +619,43 @@ static int cb_check_call(const wrnn_taco_front *f, int32_t rows, const void *wor
     if (rows < 1 || rows > (1 << 20)) CB_FAIL(WRNN_ERR_ARG, "bad length %d (1..%d)", rows, 1 << 20);
     if (workspace_bytes < wrnn_taco_front_workspace_bytes(f, rows)) CB_FAIL(WRNN_ERR_WORKSPACE, "workspace too small");
     if (((uintptr_t)workspace & 255) != 0) CB_FAIL(WRNN_ERR_ARG, "workspace must be 256-byte aligned");
+    if (f->device < 0) CB_FAIL(WRNN_ERR_NO_DEVICE, "a dims-only handle (wrnn_taco_front_debug_host_handle) launches nothing");
+    return WRNN_OK;
+}
+
+// ids -> seq_out, seq_proj_out over n rows: one sentence, or (tab) the concatenated rows of its sentences
+static int cb_encode(const wrnn_taco_front *f, const int32_t *ids, int n, const FrontTab *tab, float *seq_out, float *seq_proj_out, float *pre_rnn_out,
+                     void *workspace, hipStream_t stream)
+{
+    DeviceGuard dg(f->device);
+    CB_HIP(dg.err);
+    const CbWs s = cb_carve(f, workspace, (size_t)n);
+    const int Cin = f->enc.Cin;
+    ConvArgs a = cb_linear(f->emb, f->E, f->fc1_w, f->fc1_b, s.t0, n, f->E, f->PN1, CB_RELU);      // embedding rows -> fc1 -> ReLU
+    a.ids = ids; a.table_rows = f->n_symbols;
+    cb_launch(CB_K_ROWLIN, a, f->PN1 / 16, 1, tab, stream);
+    a = cb_linear(s.t0, f->PN1, f->fc2_w, f->fc2_b, s.x, n, f->PN1, Cin, CB_RELU);
+    cb_launch(CB_K_ROWLIN, a, Cin / 16, 1, tab, stream);
+    const int rc = cb_run_cbhg(f, f->enc, s.x, false, n, tab, s, seq_out, pre_rnn_out, stream);
+    if (rc != WRNN_OK) return rc;
+    a = cb_linear(seq_out, 2 * CB_C, f->enc_proj_w, nullptr, seq_proj_out, n, 2 * CB_C, f->D, 0);
+    cb_launch(CB_K_ROWLIN, a, f->D / 16, 1, tab, stream);
+    CB_HIP(hipGetLastError());
+    return WRNN_OK;
+}
+
+// mel ([n_mels][N]; with a table: src[s] of every sentence) -> linear_out over N rows
+static int cb_postnet(const wrnn_taco_front *f, const float *mel, int N, const FrontTab *tab, float *linear_out, float *pre_rnn_out, void *workspace,
+                      hipStream_t stream)
+{
+    DeviceGuard dg(f->device);
+    CB_HIP(dg.err);
+    const CbWs s = cb_carve(f, workspace, (size_t)N);
+    const int rc = cb_run_cbhg(f, f->post, mel, true, N, tab, s, s.ro, pre_rnn_out, stream);
+    if (rc != WRNN_OK) return rc;
+    const ConvArgs a = cb_linear(s.ro, 2 * CB_C, f->post_proj_w, nullptr, linear_out, N, 2 * CB_C, f->fft, 0);
+    cb_launch(CB_K_ROWLIN, a, f->fft / 16, 1, tab, stream);
+    CB_HIP(hipGetLastError());
     return WRNN_OK;
 }
 
@@ -487,23 +666,7 @@ extern "C" int wrnn_taco_encode(const wrnn_taco_front *f, const int32_t *ids, in
     if ((((uintptr_t)seq_out | (uintptr_t)seq_proj_out | (uintptr_t)pre_rnn_out) & 15) != 0) CB_FAIL(WRNN_ERR_ARG, "outputs must be 16-byte aligned");
     const int rc = cb_check_call(f, n, workspace, workspace_bytes);
     if (rc != WRNN_OK) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard dg(f->device);
-    CB_HIP(dg.err);
-    const CbWs s = cb_carve(f, workspace, (size_t)n);
-    const unsigned tiles = (unsigned)((n + CB_NP - 1) / CB_NP);
-    const int Cin = f->enc.Cin;
-    ConvArgs a = cb_linear(f->emb, f->E, f->fc1_w, f->fc1_b, s.t0, n, f->E, f->PN1, CB_RELU);      // embedding rows -> fc1 -> ReLU
-    a.ids = ids; a.table_rows = f->n_symbols;
-    hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3(tiles, f->PN1 / 16), dim3(NT), 0, stream, a);
-    a = cb_linear(s.t0, f->PN1, f->fc2_w, f->fc2_b, s.x, n, f->PN1, Cin, CB_RELU);
-    hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3(tiles, Cin / 16), dim3(NT), 0, stream, a);
-    const int rc2 = cb_run_cbhg(f, f->enc, s.x, false, n, s, seq_out, pre_rnn_out, stream);
-    if (rc2 != WRNN_OK) return rc2;
-    a = cb_linear(seq_out, 2 * CB_C, f->enc_proj_w, nullptr, seq_proj_out, n, 2 * CB_C, f->D, 0);
-    hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3(tiles, f->D / 16), dim3(NT), 0, stream, a);
-    CB_HIP(hipGetLastError());
-    return WRNN_OK;
+    return cb_encode(f, ids, n, nullptr, seq_out, seq_proj_out, pre_rnn_out, workspace, (hipStream_t)stream_);
 }
 
 extern "C" int wrnn_taco_postnet(const wrnn_taco_front *f, const float *mel, int32_t N, float *linear_out, float *pre_rnn_out,
@@ -513,14 +676,80 @@ extern "C" int wrnn_taco_postnet(const wrnn_taco_front *f, const float *mel, int
     if ((((uintptr_t)linear_out | (uintptr_t)pre_rnn_out) & 15) != 0) CB_FAIL(WRNN_ERR_ARG, "outputs must be 16-byte aligned");
     const int rc = cb_check_call(f, N, workspace, workspace_bytes);
     if (rc != WRNN_OK) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard dg(f->device);
-    CB_HIP(dg.err);
-    const CbWs s = cb_carve(f, workspace, (size_t)N);
-    const int rc2 = cb_run_cbhg(f, f->post, mel, true, N, s, s.ro, pre_rnn_out, stream);
-    if (rc2 != WRNN_OK) return rc2;
-    const ConvArgs a = cb_linear(s.ro, 2 * CB_C, f->post_proj_w, nullptr, linear_out, N, 2 * CB_C, f->fft, 0);
-    hipLaunchKernelGGL(wrnn_rowlin_kernel, dim3((unsigned)((N + CB_NP - 1) / CB_NP), f->fft / 16), dim3(NT), 0, stream, a);
-    CB_HIP(hipGetLastError());
+    return cb_postnet(f, mel, N, nullptr, linear_out, pre_rnn_out, workspace, (hipStream_t)stream_);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// A list of sentences per call: the sentence table (FrontTab), built on the host and passed with every launch
+// ---------------------------------------------------------------------------------------------------------
+static bool cb_len_ok(int32_t n) { return n >= 1 && n <= (1 << 20); }
+
+extern "C" size_t wrnn_taco_front_workspace_bytes_many(const wrnn_taco_front *f, const int32_t *n, int32_t n_sent)
+{
+    if (!f || !n || n_sent < 1 || n_sent > CB_MANY) return 0;
+    int32_t rows = 0;                                                       // <= 64 * 2^20
+    for (int s = 0; s < n_sent; ++s) {
+        if (!cb_len_ok(n[s])) return 0;
+        rows += n[s];
+    }
+    return wrnn_taco_front_workspace_bytes(f, rows);                        // the regions of the single call, over the concatenated rows
+}
+
+// the table of a call and its row count; `src`: NULL, or the per-sentence [n_mels][N_s] inputs
+static int cb_table(const int32_t *n, int32_t n_sent, const float *const *src, FrontTab *t, int *rows)
+{
+    if (!n) CB_FAIL(WRNN_ERR_ARG, "NULL length table");
+    if (n_sent < 1 || n_sent > CB_MANY) CB_FAIL(WRNN_ERR_ARG, "bad sentence count %d (1..%d per call)", n_sent, CB_MANY);
+    memset(t, 0, sizeof *t);
+    t->n_sent = n_sent;
+    int row = 0, tile = 0;
+    for (int s = 0; s < n_sent; ++s) {
+        if (!cb_len_ok(n[s])) CB_FAIL(WRNN_ERR_ARG, "sentence %d: bad length %d (1..%d)", s, n[s], 1 << 20);
+        if (src && !src[s]) CB_FAIL(WRNN_ERR_ARG, "sentence %d: NULL mel", s);
+        t->n[s] = n[s]; t->row0[s] = row; t->tile0[s] = tile;
+        if (src) t->src[s] = src[s];
+        row += n[s];
+        tile += (n[s] + CB_NP - 1) / CB_NP;
+    }
+    t->tile0[n_sent] = tile;
+    *rows = row;
     return WRNN_OK;
+}
+
+static int cb_check_call_many(const wrnn_taco_front *f, const int32_t *n, int32_t n_sent, const void *workspace, size_t workspace_bytes)
+{
+    if (((uintptr_t)workspace & 255) != 0) CB_FAIL(WRNN_ERR_ARG, "workspace must be 256-byte aligned");
+    const size_t need = wrnn_taco_front_workspace_bytes_many(f, n, n_sent);
+    if (workspace_bytes < need) CB_FAIL(WRNN_ERR_WORKSPACE, "workspace too small: %zu bytes, wrnn_taco_front_workspace_bytes_many says %zu", workspace_bytes, need);
+    if (f->device < 0) CB_FAIL(WRNN_ERR_NO_DEVICE, "a dims-only handle (wrnn_taco_front_debug_host_handle) launches nothing");
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_taco_encode_many(const wrnn_taco_front *f, const int32_t *ids, const int32_t *n, int32_t n_sent, float *seq_out,
+                                     float *seq_proj_out, float *pre_rnn_out, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!f || !ids || !seq_out || !seq_proj_out || !workspace) CB_FAIL(WRNN_ERR_ARG, "NULL argument");
+    FrontTab tab;
+    int rows = 0;
+    int rc = cb_table(n, n_sent, nullptr, &tab, &rows);
+    if (rc != WRNN_OK) return rc;
+    if ((((uintptr_t)seq_out | (uintptr_t)seq_proj_out | (uintptr_t)pre_rnn_out) & 15) != 0) CB_FAIL(WRNN_ERR_ARG, "outputs must be 16-byte aligned");
+    rc = cb_check_call_many(f, n, n_sent, workspace, workspace_bytes);
+    if (rc != WRNN_OK) return rc;
+    return cb_encode(f, ids, rows, &tab, seq_out, seq_proj_out, pre_rnn_out, workspace, (hipStream_t)stream_);
+}
+
+extern "C" int wrnn_taco_postnet_many(const wrnn_taco_front *f, const float *const *mel, const int32_t *N, int32_t n_sent, float *linear_out,
+                                      float *pre_rnn_out, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!f || !linear_out || !workspace) CB_FAIL(WRNN_ERR_ARG, "NULL argument");
+    if (!mel) CB_FAIL(WRNN_ERR_ARG, "NULL mel table");
+    FrontTab tab;
+    int rows = 0;
+    int rc = cb_table(N, n_sent, mel, &tab, &rows);
+    if (rc != WRNN_OK) return rc;
+    if ((((uintptr_t)linear_out | (uintptr_t)pre_rnn_out) & 15) != 0) CB_FAIL(WRNN_ERR_ARG, "outputs must be 16-byte aligned");
+    rc = cb_check_call_many(f, N, n_sent, workspace, workspace_bytes);
+    if (rc != WRNN_OK) return rc;
+    return cb_postnet(f, tab.src[0], rows, &tab, linear_out, pre_rnn_out, workspace, (hipStream_t)stream_);
 }

@@ -660,19 +660,19 @@ struct BigruArgs {
     int T;
 };
 
-__global__ __launch_bounds__(GR_NT, 1) void wrnn_bigru_kernel(const BigruArgs a)
+// one direction of one sequence: gi [T][384], w_hh [384][128], b_hh [384], out [T][256] (this direction's half of every row is written)
+__device__ __forceinline__ void gr_direction(const float *gi, const float *w_hh, const float *b_hh, float *out, int T, int dir)
 {
     __shared__ __attribute__((aligned(16))) float hs[GR_H];
     __shared__ float gs[GR_NT];
-    const int j = threadIdx.x, dir = blockIdx.x, T = a.T;
-    const float *gi = a.gi[dir];
+    const int j = threadIdx.x;
     float wr[GR_H];
 #pragma unroll
     for (int k = 0; k < GR_H; k += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(a.w_hh[dir] + (size_t)j * GR_H + k);
+        const float4 v = *reinterpret_cast<const float4 *>(w_hh + (size_t)j * GR_H + k);
         wr[k] = v.x; wr[k + 1] = v.y; wr[k + 2] = v.z; wr[k + 3] = v.w;
     }
-    const float bh = a.b_hh[dir][j];
+    const float bh = b_hh[j];
     if (j < GR_H) hs[j] = 0.f;
     __syncthreads();
     float h = 0.f;                                                     // thread u < 128: h[u]
@@ -700,11 +700,32 @@ __global__ __launch_bounds__(GR_NT, 1) void wrnn_bigru_kernel(const BigruArgs a)
             const float ng = tanhf(g2 + rg * gs[2 * GR_H + j]);
             h = (h - ng) * zg + ng;
             hs[j] = h;
-            a.out[(size_t)t * (2 * GR_H) + dir * GR_H + j] = h;
+            out[(size_t)t * (2 * GR_H) + dir * GR_H + j] = h;
             g0 = n0; g1 = n1; g2 = n2;
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(GR_NT, 1) void wrnn_bigru_kernel(const BigruArgs a)
+{
+    const int dir = blockIdx.x;
+    gr_direction(a.gi[dir], a.w_hh[dir], a.b_hh[dir], a.out, a.T, dir);
+}
+
+// wrnn_bigru_many_kernel: grid (2, n_seq); workgroup (dir, s) is wrnn_bigru_kernel's workgroup `dir` on sequence s -- rows [row0[s], row0[s] + T[s])
+// of gi and out -- with the weights all sequences share.  No workgroup waits for another.
+constexpr int GR_MANY = WRNN_TACO_FRONT_MANY_MAX;
+struct BigruManyArgs {
+    BigruArgs a;               // gi / out: the concatenated tensors (a.T unused)
+    int T[GR_MANY], row0[GR_MANY];
+};
+
+__global__ __launch_bounds__(GR_NT, 1) void wrnn_bigru_many_kernel(const BigruManyArgs m)
+{
+    const int dir = blockIdx.x, s = blockIdx.y;
+    const size_t r0 = (size_t)m.row0[s];
+    gr_direction(m.a.gi[dir] + r0 * GR_NT, m.a.w_hh[dir], m.a.b_hh[dir], m.a.out + r0 * (2 * GR_H), m.T[s], dir);
 }
 
 }  // namespace wrnn
@@ -811,5 +832,33 @@ extern "C" int wrnn_bigru(int device, const wrnn_bigru_call *c)
     hipLaunchKernelGGL(wrnn_bigru_kernel, dim3(2), dim3(GR_NT), 0, reinterpret_cast<hipStream_t>(c->stream), a);
     e = hipGetLastError();
     if (e != hipSuccess) { taco_err("wrnn_bigru_kernel launch: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    return WRNN_OK;
+}
+
+// n_seq sequences, one weight set, one launch (see wrnn_bigru_many_kernel)
+extern "C" int wrnn_bigru_many(int device, const wrnn_bigru_many_call *c)
+{
+    if (!c || c->struct_bytes != sizeof(wrnn_bigru_many_call)) { taco_err("null argument / struct size mismatch"); return WRNN_ERR_ARG; }
+    if (c->n_seq < 1 || c->n_seq > GR_MANY) { taco_err("bad call: n_seq=%d (1..%d)", c->n_seq, GR_MANY); return WRNN_ERR_ARG; }
+    if (c->hidden != GR_H || !c->T || !c->gi_fwd || !c->gi_rev || !c->w_hh_fwd || !c->w_hh_rev || !c->b_hh_fwd || !c->b_hh_rev || !c->out) {
+        taco_err("bad call: hidden=%d (this build: %d) or a null buffer", c->hidden, GR_H);
+        return WRNN_ERR_ARG;
+    }
+    BigruManyArgs m;
+    memset(&m, 0, sizeof m);
+    long row = 0;
+    for (int s = 0; s < c->n_seq; ++s) {
+        if (c->T[s] < 1 || c->T[s] > (1 << 20)) { taco_err("sequence %d: bad length T=%d (1..%d)", s, c->T[s], 1 << 20); return WRNN_ERR_ARG; }
+        m.T[s] = c->T[s]; m.row0[s] = (int)row;
+        row += c->T[s];
+    }
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    m.a.gi[0] = c->gi_fwd; m.a.gi[1] = c->gi_rev; m.a.w_hh[0] = c->w_hh_fwd; m.a.w_hh[1] = c->w_hh_rev; m.a.b_hh[0] = c->b_hh_fwd; m.a.b_hh[1] = c->b_hh_rev;
+    m.a.out = c->out;
+    hipLaunchKernelGGL(wrnn_bigru_many_kernel, dim3(2, (unsigned)c->n_seq), dim3(GR_NT), 0, reinterpret_cast<hipStream_t>(c->stream), m);
+    e = hipGetLastError();
+    if (e != hipSuccess) { taco_err("wrnn_bigru_many_kernel launch: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
     return WRNN_OK;
 }

@@ -10,7 +10,9 @@ abbreviation expansion need the reference's text front-end (out of scope).
 
 `--batch N` (with --batched): all sentences at once -- the Tacotron decoder loops in groups of N <= 8 sentences per persistent kernel
 (`TacotronInference.generate_batch`, csrc/wrnn_taco_batch.hip), then ONE vocoder pass over all of them (`generate_corpus`, noise drawn inside the
-library under the seeds --seed, --seed + 1, ...).  Same file names.  Without the flag the per-sentence path runs as before."""
+library under the seeds --seed, --seed + 1, ...).  Same file names.  With --cbhg_kernel the encoder and the post-net of all sentences run side by
+side as well (`wrnn_taco_encode_many` / `wrnn_taco_postnet_many`, one call each per 64 sentences).  Without the flag the per-sentence path runs as
+before."""
 import argparse
 import time
 from pathlib import Path
@@ -36,7 +38,7 @@ def main(argv=None):
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--steps', type=int, default=2000, help='decoder step limit (Tacotron.generate default)')
     ap.add_argument('--output', default='.', help='output directory')
-    ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet)')
+    ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet; with --batch their _many forms)')
     ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (needs --batched)')
     ap.add_argument('--seed', type=int, default=0, help='--batch: sentence i draws its sampling noise under seed + i')
     ap.set_defaults(batched=True)

@@ -269,6 +269,72 @@ class TacotronInference:
             raise _lib.WrnnError(f'wrnn_taco_postnet failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
         return linear, pre
 
+    def _front_workspace_many(self, lengths):
+        """(workspace, the HOST int32 array of `lengths`) for one `_many` call; ValueError for a table the library refuses."""
+        import ctypes
+        from . import _lib
+        n = (ctypes.c_int32 * len(lengths))(*lengths)
+        need = int(_lib.lib().wrnn_taco_front_workspace_bytes_many(self._front, n, len(lengths)))
+        if need == 0:
+            raise ValueError(f'{len(lengths)} sentences of lengths {list(lengths)}: 1..{_lib.TACO_FRONT_MANY_MAX} sentences of 1..2^20 rows per call')
+        if self._front_ws is None or self._front_ws.numel() < need:
+            self._front_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._front_ws, n
+
+    def encode_kernel_many(self, list_of_ids, want_pre_rnn=False):
+        """`encode_kernel` for a list of 1..64 sentences through ONE `wrnn_taco_encode_many` call (one host-to-device copy of the concatenated
+        ids, every stage one launch for all sentences).  Returns per sentence (encoder_seq (1, n, 2C), its projection (1, n, D), the highway
+        output (n, C) or None): views of the call's concatenated outputs, each bit-identical to `encode_kernel` of that sentence alone.
+        Asynchronous on the current stream."""
+        from . import _lib
+        L, h = _lib.lib(), self._front_handle()
+        if h is None:
+            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
+        dev = self.device
+        lengths = [len(ids) for ids in list_of_ids]
+        ws, n = self._front_workspace_many(lengths)
+        rows = sum(lengths)
+        ids_d = torch.as_tensor([int(i) for ids in list_of_ids for i in ids], dtype=torch.int32, device='cpu').to(dev)
+        seq = torch.empty(rows, self.p['encoder_proj.weight'].shape[1], device=dev)
+        seq_proj = torch.empty(rows, self.p['encoder_proj.weight'].shape[0], device=dev)
+        pre = torch.empty(rows, seq.size(1) // 2, device=dev) if want_pre_rnn else None
+        rc = L.wrnn_taco_encode_many(h, ids_d.data_ptr(), n, len(lengths), seq.data_ptr(), seq_proj.data_ptr(), pre.data_ptr() if want_pre_rnn else None,
+                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_encode_many failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        out, o = [], 0
+        for k in lengths:
+            out.append((seq[o:o + k].unsqueeze(0), seq_proj[o:o + k].unsqueeze(0), pre[o:o + k] if want_pre_rnn else None))
+            o += k
+        return out
+
+    def postnet_kernel_many(self, list_of_mels, want_pre_rnn=False):
+        """`postnet_kernel` for a list of 1..64 mels ((1, n_mels, N_s) or (n_mels, N_s) each) through ONE `wrnn_taco_postnet_many` call.  Returns per
+        sentence (linear (N_s, fft), the highway output (N_s, C) or None): views of the call's concatenated outputs, each bit-identical to
+        `postnet_kernel` of that mel alone.  Asynchronous on the current stream."""
+        import ctypes
+        from . import _lib
+        L, h = _lib.lib(), self._front_handle()
+        if h is None:
+            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
+        dev = self.device
+        ms = [mel.reshape(self.n_mels, -1).to(dev, torch.float32).contiguous() for mel in list_of_mels]
+        lengths = [m.size(1) for m in ms]
+        ws, n = self._front_workspace_many(lengths)
+        rows = sum(lengths)
+        linear = torch.empty(rows, self.p['post_proj.weight'].shape[0], device=dev)
+        pre = torch.empty(rows, self.p['post_proj.weight'].shape[1] // 2, device=dev) if want_pre_rnn else None
+        ptrs = (ctypes.c_void_p * len(ms))(*[m.data_ptr() for m in ms])
+        rc = L.wrnn_taco_postnet_many(h, ptrs, n, len(ms), linear.data_ptr(), pre.data_ptr() if want_pre_rnn else None, ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_postnet_many failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        out, o = [], 0
+        for k in lengths:
+            out.append((linear[o:o + k], pre[o:o + k] if want_pre_rnn else None))
+            o += k
+        return out
+
     def encode(self, ids):
         """Encoder (:24-39) + `encoder_proj` (:403-404): ids (n,) -> encoder_seq (1, n, 2C), its projection (1, n, D)."""
         x = torch.as_tensor(ids, dtype=torch.long, device=self.device).unsqueeze(0)
@@ -432,10 +498,13 @@ class TacotronInference:
     def generate_batch(self, list_of_ids, steps=2000, kernel=True, cbhg_kernel=False, max_batch=8):
         """`generate()` for a list of sentences: a list of (mel, linear, attention), one per sentence, as `generate()` returns them.
 
-        kernel=True (HIP device): the encoder and the post-net run per sentence as in `generate(kernel=True, cbhg_kernel=...)`; the decoder loops
-        run in groups of at most `max_batch` (1..8) sentences through `wrnn_taco_decode_batch` -- one persistent kernel per group, every
-        sentence ending on its own stop test, each result bit-identical to the single-sentence kernel's.  A sentence of more than
-        `_lib.TACO_BATCH_NMAX` ids goes through the single-sentence kernel.  kernel=False: a loop of `generate()`, on any device."""
+        kernel=True (HIP device): the decoder loops run in groups of at most `max_batch` (1..8) sentences through `wrnn_taco_decode_batch` -- one
+        persistent kernel per group, every sentence ending on its own stop test, each result bit-identical to the single-sentence kernel's.  A
+        sentence of more than `_lib.TACO_BATCH_NMAX` ids goes through the single-sentence kernel.  cbhg_kernel=False: the encoder and the post-net
+        run per sentence on the torch ops, as in `generate(kernel=True)`.  cbhg_kernel=True: ONE `wrnn_taco_encode_many` call encodes all
+        sentences in front of the decoder groups and ONE `wrnn_taco_postnet_many` call runs the post-net over all decoded mels (64 sentences per
+        call at most; a call of one sentence takes the single-sentence entry points), each sentence's bits those of `generate(kernel=True,
+        cbhg_kernel=True)`; the results reach the host in one transfer at the end.  kernel=False: a loop of `generate()`, on any device."""
         from . import _lib
         if not kernel:
             return [self.generate(ids, steps=steps, kernel=False, cbhg_kernel=cbhg_kernel) for ids in list_of_ids]
@@ -447,20 +516,42 @@ class TacotronInference:
         self._bigru_kernel = True
         front = bool(cbhg_kernel) and self._front_handle() is not None
         self.last_front_path = 'hip' if front else 'torch'
-        encs = [(self.encode_kernel(ids)[:2] if front else self.encode(ids)) for ids in list_of_ids]
+        M = _lib.TACO_FRONT_MANY_MAX
+        if front:
+            # all sentences side by side, <= 64 per call; a call of ONE sentence goes through the single-sentence entry point (the same bits; the
+            # sentence table costs 1-2 % there: DESIGN.md section 6)
+            enc_many = lambda chunk: self.encode_kernel_many(chunk) if len(chunk) > 1 else [self.encode_kernel(chunk[0])]
+            post_many = lambda chunk: self.postnet_kernel_many(chunk) if len(chunk) > 1 else [self.postnet_kernel(chunk[0])]
+            encs = [e[:2] for c in range(0, len(list_of_ids), M) for e in enc_many(list_of_ids[c:c + M])]
+        else:
+            encs = [self.encode(ids) for ids in list_of_ids]
         decoded = [None] * len(encs)
         short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
         for g in range(0, len(short), int(max_batch)):
             group = short[g:g + int(max_batch)]
             for i, d in zip(group, self._decode_batch_kernel([encs[i] for i in group], steps)):
                 decoded[i] = d
+        if front:
+            for i, e in enumerate(encs):
+                if decoded[i] is None:
+                    decoded[i] = self._decode_kernel(e[0], e[1], steps)
+            # one post-net pass over all decoded mels (<= 64 per call), then ONE transfer: every result flattened into one device buffer
+            mels = [d[0] for d in decoded]
+            lins = [l for c in range(0, len(mels), M) for l, _ in post_many(mels[c:c + M])]
+            parts = [t.reshape(-1) for (mel, attn), lin in zip(decoded, lins) for t in (mel[0], lin, attn)]
+            flat = torch.cat(parts).cpu().numpy() if parts else None
+            out, o = [], 0
+            for (mel, attn), lin in zip(decoded, lins):
+                trio = []
+                for t in (mel[0], lin, attn):
+                    trio.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
+                    o += t.numel()
+                out.append((trio[0], trio[1].T, trio[2]))                          # linear (fft, N), as `generate()` returns it
+            return out
         out = []
         for i, e in enumerate(encs):
             mel, attn = decoded[i] if decoded[i] is not None else self._decode_kernel(e[0], e[1], steps)
-            if front:
-                linear = self.postnet_kernel(mel)[0].transpose(0, 1)
-            else:
-                linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+            linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
             out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
         return out
 
