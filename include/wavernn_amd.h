@@ -66,6 +66,14 @@ enum {
                                waves (W_ih and W_hh of the CU's 16 units in registers, the fc tile in LDS: operand by LDS-DMA, MFMA block, partial tiles)
                                and four service waves (partial sums, GRU cell, publishes, conditioning, fc3 + sampling) that meet through LDS counters;
                                gh never leaves the CU.  Same split, workspace, exchange buffer and state layout as WRNN_ALGO_DUO (csrc/wrnn_octo.hip) */
+    WRNN_ALGO_TILE = 10,    /* wrnn_generic_kernel's dataflow for a TILE of up to 16 segments per workgroup (csrc/wrnn_tile.hip; on request only, `auto` never
+                               picks it): generic packs only -- non-shipped dims, or RAW with more than 512 classes --, the pack as it is; ceil(n_segments / 16)
+                               workgroups that never wait for one another, every matrix product on v_mfma_f32_16x16x4_f32 with the 16 segments as its N, so the
+                               weights are streamed once per 16 segments and step.  Whole calls only (no step range), no mel_stage, no sparse_groups; workspace,
+                               noise_lib, progress, timer and info as on wrnn_generic_kernel.  THE LDS RULE: the activations of the 16 segments live in LDS,
+                               16 * 4 * (up4(1 + feat + aux) + 2 * up4(max(rnn, fc) + aux) + 2 * up4(rnn)) + 2560 bytes (up4: rounded up to a multiple of 4),
+                               and must fit one CU's 160 KiB = 163840 (rnn = fc = 512, feat 80, aux 32: 145152; rnn = fc = 576 still fits, 640 does not); RAW: <= 2048
+                               classes.  Other dims: WRNN_ERR_ARG with the bytes needed -- stay on `auto` */
     WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
                                four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
                                (wrnn_pack_sparse_blocks) and >= 256 CUs; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
@@ -119,7 +127,7 @@ typedef struct wrnn_timer wrnn_timer;
 
 /* What a wrnn_generate* call decided (filled synchronously, before the call returns). */
 typedef struct wrnn_run_info {
-    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_octo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" */
+    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_octo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" / "wrnn_tile_kernel" */
     int32_t units_per_wg;    /* hidden units per workgroup (16; sparse: 64; stream: 0) */
     int32_t clusters;        /* independent CU clusters, each holding one copy of the weights */
     int32_t depth;           /* groups of <= 16 segments in flight per cluster */

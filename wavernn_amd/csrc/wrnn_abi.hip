@@ -26,6 +26,9 @@ int loop_max_depth(int mode);
 size_t loop_state_floats(int G);
 hipError_t launch_generic(const GenArgs &args, int mode, hipStream_t stream);
 bool generic_dims_ok(int H, int F, int M, int A, int C, int mode);
+hipError_t launch_tile(const GenArgs &args, int mode, hipStream_t stream);
+size_t tile_lds_bytes(int H, int F, int M, int A, int C);
+bool tile_dims_ok(int H, int F, int M, int A, int C, int mode);
 hipError_t launch_duo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int duo_max_depth();
 size_t duo_xbuf_bytes(int G);
@@ -428,7 +431,7 @@ int enqueue_progress(const wrnn_options *o, int done, int T, int n, hipStream_t 
     return WRNN_OK;
 }
 
-enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, N_KINDS };
+enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, N_KINDS };
 constexpr int DUO_TAB_FPS = 8;       // rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
 constexpr bool DUO_AUTO = true;      // `auto` runs MoL on wrnn_duo_kernel at every depth (round 4, profiles/r04a_probe_new.json: 13.5 vs 16.6 us per step
                                      // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
@@ -473,6 +476,8 @@ const KindDesc KINDS[N_KINDS] = {
     /* K_SPARSE  */ {"wrnn_sparse_kernel", 64, 3, true, true, true, sparse_clusters, [](int) { return 1; }, sparse_state_floats,
                      sparse_xbuf_bytes, sparse_xbuf_bytes,
                      [](const LoopArgs &a, int, int nbp, int mode, hipStream_t s) { return launch_sparse(a, nbp, mode, s); }},
+    // (wrnn_generic_kernel's dataflow and pack, one workgroup per 16 segments; on request)
+    /* K_TILE    */ {"wrnn_tile_kernel", 16, 0, false, false, false},
 };
 
 // what a call will run: kernel, split, rounds, slab length
@@ -565,7 +570,7 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     const bool partial = pl->t0 != 0 || pl->t1 != T;
     const int algo = o->algo;
     if (algo != WRNN_ALGO_AUTO && algo != WRNN_ALGO_STREAM && algo != WRNN_ALGO_LOOP && algo != WRNN_ALGO_SPARSE && algo != WRNN_ALGO_DUO && algo != WRNN_ALGO_CHAIN &&
-        algo != WRNN_ALGO_OCTO) {
+        algo != WRNN_ALGO_OCTO && algo != WRNN_ALGO_TILE) {
         set_err("unknown algo %d", algo);
         return WRNN_ERR_ARG;
     }
@@ -580,7 +585,23 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     const bool two_groups = o->sparse_groups == 2;
     const int groups = (B + SEG - 1) / SEG;
     pl->kind = K_STREAM; pl->ncl = 0; pl->G = 0; pl->rounds = 1; pl->per_round = B; pl->slab = T; pl->ngr_max = groups;
-    if (p->generic) {           // non-shipped hparams: the dimension-generic kernel is the only one that takes them
+    if (algo == WRNN_ALGO_TILE) {       // on request only: wrnn_generic_kernel's dataflow for 16 segments per workgroup (csrc/wrnn_tile.hip)
+        if (!p->generic) {
+            set_err("wrnn_tile_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo auto "
+                    "picks its kernel", H);
+            return WRNN_ERR_ARG;
+        }
+        if (!tile_dims_ok(p->gH, p->gF, p->gM, p->gA, p->C, p->mode)) {
+            set_err("wrnn_tile_kernel: rnn %d, fc %d, feat %d, aux %d, %d classes need %zu bytes of LDS per workgroup, the limit is %d (and RAW: <= 2048 classes); "
+                    "algo auto runs this pack on wrnn_generic_kernel", p->gH, p->gF, p->gM, p->gA, p->C, tile_lds_bytes(p->gH, p->gF, p->gM, p->gA, p->C), 160 * 1024);
+            return WRNN_ERR_ARG;
+        }
+        if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
+        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_kernel)"); return WRNN_ERR_ARG; }
+        pl->kind = K_TILE;
+        return WRNN_OK;
+    }
+    if (p->generic) {           // non-shipped hparams: the dimension-generic kernel is the only one that takes them without being asked for by name
         if (algo != WRNN_ALGO_AUTO && algo != WRNN_ALGO_STREAM) {
             set_err("this pack has non-shipped dims (rnn %d, fc %d, feat %d, aux %d): only the generic kernel (algo auto / stream) runs it", p->gH, p->gF, p->gM, p->gA);
             return WRNN_ERR_ARG;
@@ -686,7 +707,7 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
     l.xcc = o;    o = al(o + XCC_WORDS * sizeof(unsigned));
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
-    if (pl.kind == K_GENERIC) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE) {
         l.nlib = o; if (noise_lib) o = al(o + (size_t)T * noise_row);
         l.total = o;
         return l;
@@ -860,7 +881,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         HIPCHK(hipMemcpyAsync(ws + l.segs + (size_t)2 * B * sizeof(int), o->seg_moff, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
         HIPCHK(launch_put_floats((float *)(ws + l.melc), coef, 3 * LAST_SCALE, stream));       // (by value, as kernel arguments: `coef` is a stack array)
     }
-    if (pl.kind == K_GENERIC) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE) {
         GenArgs g;
         memset(&g, 0, sizeof g);
         g.I_T = p->g_I_T; g.I_b = p->I_b; g.w_ih1T = p->w_ih1T; g.w_hh1T = p->w_hh1T; g.b_ih1 = p->b_ih1; g.b_hh1 = p->b_hh1;
@@ -874,7 +895,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         }
         g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-        HIPCHK(launch_generic(g, p->tr.mode, stream));
+        HIPCHK(pl.kind == K_TILE ? launch_tile(g, p->tr.mode, stream) : launch_generic(g, p->tr.mode, stream));
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         wrnn_run_info gi;
         memset(&gi, 0, sizeof gi);

@@ -18,6 +18,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ._lib import ALGOS
 from .batch import generate_corpus
 from .dsp import save_wav
 from .model import WaveRNN
@@ -54,6 +55,9 @@ def main(argv=None):
                     help='where the sampling noise comes from (default: cpu with --seed, else device); cpu and library need --seed')
     ap.add_argument('--sparse-groups', type=int, default=None, choices=[1, 2],
                     help='a pruned MoL model on wrnn_sparse_kernel: groups of segments per cluster (2: 512 segments a round; a dense model ignores it)')
+    ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
+                    help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
+                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup")
     a = ap.parse_args(argv)
     if a.noise in ('cpu', 'library') and a.seed is None:
         ap.error(f'--noise {a.noise} needs --seed')
@@ -74,6 +78,7 @@ def main(argv=None):
     if a.weights:
         model.load(a.weights)
     model.sparse_groups = a.sparse_groups
+    model.loop_algo = a.algo
     paths, mels = load_mels(a.mels)
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
     outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group,

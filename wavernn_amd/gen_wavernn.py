@@ -11,6 +11,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ._lib import ALGOS
 from .model import WaveRNN
 from .synthetic import SHIPPED
 
@@ -55,6 +56,9 @@ def main(argv=None):
     ap.add_argument('--noise', choices=['cpu', 'device', 'library'], default=None,
                     help="cpu (default): the reference's CPU stream after torch.manual_seed(--seed); device: torch's device generator; library: drawn inside "
                          'the loop from a counter-based generator -- the utterance sounds the same alone and in any gen_corpus batch with the same seed')
+    ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
+                    help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
+                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup")
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -65,6 +69,7 @@ def main(argv=None):
     if a.device_noise and a.noise not in (None, 'device'):
         ap.error('--device-noise contradicts --noise ' + a.noise)
     model.noise_source = 'device' if a.device_noise else (a.noise or 'cpu')
+    model.loop_algo = a.algo
     if a.seed is not None:
         torch.manual_seed(a.seed)
         model.noise_seed = a.seed
