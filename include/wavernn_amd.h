@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 9   /* v9 + wrnn_options.noise_lib / noise_seed / noise_seg_id, wrnn_noise_fill, wrnn_noise_fill_host (appended like sparse_groups: the number stays): the sampling noise drawn inside the library.  v9 + wrnn_options.sparse_groups (appended; struct_bytes tells whether a caller has it: the number stays, every v9 caller runs as it did): two groups per cluster of wrnn_sparse_kernel, on request.  v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
+#define WRNN_ABI_VERSION 9   /* v9 + wrnn_nll, wrnn_nll_host (appended like wrnn_noise_fill: the number stays, the symbols tell whether a library has them): the loss of a teacher-forced call.  v9 + wrnn_options.noise_lib / noise_seed / noise_seg_id, wrnn_noise_fill, wrnn_noise_fill_host (appended like sparse_groups: the number stays): the sampling noise drawn inside the library.  v9 + wrnn_options.sparse_groups (appended; struct_bytes tells whether a caller has it: the number stays, every v9 caller runs as it did): two groups per cluster of wrnn_sparse_kernel, on request.  v9 (round 6): wrnn_pack_sparse_fc_blocks -- block-sparse Linear layers in wrnn_sparse_kernel.  v8 (round 6): WRNN_ALGO_OCTO (wrnn_octo_kernel: one 512-thread workgroup per CU, matrix waves + service waves; dense MOL).  v7 (round 5): WRNN_ALGO_CHAIN (wrnn_chain_kernel, what `auto` runs for <= 128 segments of a dense model, MOL or 9-bit RAW); WRNN_ALGO_SPARSE is the rebuilt wrnn_sparse_kernel (slabbed, resumable, takes mel_stage) and what `auto` picks for a qualifying pack; wrnn_options.depth does not apply to it.  v6 (round 4): wrnn_options.mel_stage & co + wrnn_pre_upsample_rows -- the last up-sampling stage formed inside wrnn_duo_kernel.  v5 (round 4): WRNN_ALGO_DUO runs RAW too; `auto` never degrades inside the library (WRNN_ERR_RESIDENCY: the caller re-plans); tuning bits per kernel */
 
 enum {
     WRNN_OK = 0,
@@ -173,8 +173,10 @@ typedef struct wrnn_options {
                                   workgroup instead of folded into the fc2 tiles (RAW: no effect -- y2 is always published); wrnn_chain_kernel: bit 5 = MoL's fc3 tiles read from LDS (round 5).
                                 When the two-workgroups-per-CU grid of wrnn_duo_kernel is refused the call returns WRNN_ERR_RESIDENCY; the
                                 caller may run it again with WRNN_ALGO_LOOP (another workspace layout: query its size) or _STREAM. */
-    const float *force_x;    /* test hook, device [n,T]: value fed back as x_t instead of the sample (teacher forcing) */
-    float *logits;           /* test hook, device [T,n,C]: fc3 output of every step (:223) */
+    const float *force_x;    /* device [n,T]: value fed back as x_t instead of the sample (teacher forcing): the waveform a scoring call walks
+                                (wrnn_nll's `target`), and what the parity tests feed to compare logits step by step */
+    float *logits;           /* device [T,n,C]: fc3 output of every step (:223) -- with force_x the output of the reference's teacher-forced
+                                `WaveRNN.forward` (:131-167), what wrnn_nll scores; also read by the parity tests */
     unsigned long long *phase_clocks; /* profiling hook, device [256 workgroups][32] zeroed by the caller: wrnn_loop_kernel (MOL and RAW) and
                                 wrnn_duo_kernel (MOL) add their per-(phase, stage segment) shader clocks (layouts: csrc/wrnn_loop.hip,
                                 csrc/wrnn_duo.hip, "PROF"); with tuning bit 6: the placement read-out of wrnn_duo / _sparse_kernel instead */
@@ -298,6 +300,40 @@ int wrnn_noise_fill(int mode, int32_t n_segments, int32_t n_classes, int32_t t_b
                     float *out, int device, void *stream);
 int wrnn_noise_fill_host(int mode, int32_t n_segments, int32_t n_classes, int32_t t_begin, int32_t t_end, uint64_t seed, const uint64_t *seg_id,
                          float *out);
+
+/*
+ * The loss of a teacher-forced call (appended to ABI v9: the symbols tell whether a library has them): -log p of the waveform a
+ * wrnn_generate* call was fed through wrnn_options.force_x, from the fc3 outputs it left in wrnn_options.logits -- what the reference's training
+ * and validation compute on `WaveRNN.forward` (train_wavernn.py:83, :123): MOL `discretized_mix_logistic_loss` (utils/distribution.py:16-84 with
+ * its defaults num_classes = 65536, log_scale_min = log(1e-14)), RAW `F.cross_entropy`.  float32 arithmetic, like the reference's.
+ *   logits   [T][n_segments][n_classes], exactly the tensor wrnn_options.logits received
+ *   target   [n_segments][T], exactly the force_x tensor of that call: MOL the sample value in [-1, 1]; RAW the class value 2 idx / (C - 1) - 1
+ *            (the class is recovered as rint((x + 1) (C - 1) / 2), exact for C <= 2048, and clamped into [0, C))
+ *   seg_len  int32 [n_segments] or NULL (every step counts): step t of segment b counts iff t < seg_len[b] (values outside [0, T] are clamped)
+ *   nll      NULL, or float32 [n_segments][T]: -log p of every counted step, 0 for every step past seg_len
+ *   sum      float64 [n_segments]: the sum of the segment's counted per-step float32 values, accumulated in float64 in a fixed order (steps
+ *            t = s mod S in step order for each of S slots -- MOL 64, RAW 16 --, then the slots in order) without atomics: two runs give the
+ *            same bits, and a segment's values and sum do not depend on the other segments of the call (one workgroup per segment).
+ * wrnn_nll: DEVICE pointers; asynchronous on `stream`; no allocation, no synchronisation.  wrnn_nll_host: the same struct with HOST pointers
+ * (`stream` ignored), computed by the calling thread, the HIP runtime is not touched; the two differ by their expf / logf / log1pf and, within a
+ * step, by the order of the sums over the mixtures / classes.  WRNN_ERR_ARG with a message, before anything is launched: a struct size
+ * mismatch, a NULL logits / target / sum, MOL with n_classes != 30, RAW with n_classes outside 2..2048, n_segments < 1 or T < 1.  wrnn_nll without
+ * a device: WRNN_ERR_NO_DEVICE, behind those checks.
+ */
+typedef struct wrnn_nll_call {
+    uint32_t struct_bytes;
+    int32_t mode;            /* WRNN_MODE_* */
+    int32_t n_classes;       /* MOL: 30; RAW: 2..2048 */
+    int32_t n_segments, T;
+    const float *logits;
+    const float *target;
+    const int32_t *seg_len;
+    float *nll;
+    double *sum;
+    void *stream;
+} wrnn_nll_call;
+int wrnn_nll(int device, const wrnn_nll_call *c);
+int wrnn_nll_host(const wrnn_nll_call *c);
 
 /* What wrnn_generate_segments WOULD run for this many segments under these options (kernel, split, rounds, slab length),
  * without launching anything.  `launches` is left 0. */

@@ -23,7 +23,7 @@ ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': 
 #: every symbol include/wavernn_amd.h declares
 EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_create', 'wrnn_pack_destroy',
            'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
-           'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
+           'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_nll', 'wrnn_nll_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_workspace_bytes_many',
            'wrnn_pre_upsample_many', 'wrnn_pre_debug_host_handle', 'wrnn_pre_last_error',
@@ -155,6 +155,17 @@ class Options(ctypes.Structure):
         self.struct_bytes = ctypes.sizeof(Options)
 
 
+class NllCall(ctypes.Structure):
+    """wrnn_nll_call: the loss of a teacher-forced call (wrnn_nll: device pointers; wrnn_nll_host: host pointers)."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('mode', ctypes.c_int32), ('n_classes', ctypes.c_int32), ('n_segments', ctypes.c_int32),
+                ('T', ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ('logits', 'target', 'seg_len', 'nll', 'sum', 'stream')]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = ctypes.sizeof(NllCall)
+
+
 #: wrnn_options.progress: void (*)(int32 steps_done, int32 T, int32 n_segments, void *user)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p)
 
@@ -221,6 +232,8 @@ def lib():
     L.wrnn_noise_fill.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.wrnn_noise_fill_host.argtypes = L.wrnn_noise_fill.argtypes[:8]
+    L.wrnn_nll.argtypes = [ctypes.c_int, ctypes.POINTER(NllCall)]
+    L.wrnn_nll_host.argtypes = [ctypes.POINTER(NllCall)]
     L.wrnn_plan_segments.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Options), ctypes.POINTER(RunInfo)]
     L.wrnn_timer_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_timer_destroy.argtypes = [ctypes.c_void_p]
@@ -287,6 +300,25 @@ def lib():
 def check(rc, what):
     if rc != WRNN_OK:
         raise WrnnError(f'{what} failed (rc={rc}): {lib().wrnn_last_error().decode()}')
+
+
+def nll_host(mode, logits, target, seg_len=None, per_step=True):
+    """`wrnn_nll_host`: the loss `wrnn_nll` computes on the device, by the calling thread.  logits (T, n, C) and target (n, T) float32 host arrays in
+    the layouts of wrnn_options.logits / force_x, seg_len (n,) int32 or None.  Returns (nll (n, T) float32 or None, sum (n,) float64).  No HIP
+    device is needed."""
+    import numpy as np
+    logits, target = np.ascontiguousarray(logits, np.float32), np.ascontiguousarray(target, np.float32)
+    T, n, C = logits.shape
+    if target.shape != (n, T):
+        raise ValueError(f'target has shape {target.shape}, the logits ask for {(n, T)}')
+    lens = None if seg_len is None else np.ascontiguousarray(seg_len, np.int32)
+    if lens is not None and lens.shape != (n,):
+        raise ValueError('seg_len: one int32 per segment')
+    nll, total = (np.empty((n, T), np.float32) if per_step else None), np.empty(n, np.float64)
+    c = NllCall(mode=MODE_MOL if mode == 'MOL' else MODE_RAW, n_classes=C, n_segments=n, T=T, logits=logits.ctypes.data, target=target.ctypes.data,
+                seg_len=None if lens is None else lens.ctypes.data, nll=None if nll is None else nll.ctypes.data, sum=total.ctypes.data)
+    check(lib().wrnn_nll_host(ctypes.byref(c)), 'wrnn_nll_host')
+    return nll, total
 
 
 def noise_fill_host(mode, n_segments, n_classes, t_begin, t_end, seed, seg_id=None):

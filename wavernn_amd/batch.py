@@ -202,6 +202,16 @@ def chunk_utterances(plan: Plan, lo: int, hi: int, max_segments: int):
     return chunks
 
 
+def score_corpus(model, mels: Sequence, wavs: Sequence, mu_law: Optional[bool] = None, per_step: bool = False, algo: Optional[str] = None,
+                 timings: Optional[dict] = None):
+    """Teacher-forced negative log-likelihood of n utterances (`score.score_corpus`): they become the n unfolded segments of ONE segment table per
+    chunk -- seg_pos = o_u, seg_lim = o_u + the utterance's counted steps, T = the longest --, run by one loop call with `force_x` and `logits`
+    and scored by one `wrnn_nll` launch on the same stream.  Chunks keep the logits under `model.score_logits_bytes`; the results come back in
+    the caller's order."""
+    from .score import score_corpus as _score_corpus
+    return _score_corpus(model, mels, wavs, mu_law=mu_law, per_step=per_step, algo=algo, timings=timings)
+
+
 def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bool, seeds: Optional[Sequence[int]] = None,
                     group=None, loop_fn=None, return_segments=False, noise_source='cpu', finish='all', check=True,
                     max_segments_per_launch: int = 4096, shard=None, ranks: Optional[int] = None, timings: Optional[dict] = None):

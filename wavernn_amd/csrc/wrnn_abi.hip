@@ -20,6 +20,9 @@ hipError_t launch_cond_frag(const CondArgs &a, int n_cus, hipStream_t stream);
 hipError_t launch_noise_mol(const float *in, float *out, long n, int B, int n_cus, hipStream_t stream);
 hipError_t launch_noise_fill(bool mol, int B, int C, int t0, int t1, uint64_t seed, const uint64_t *seg_id, float *out, int n_cus, hipStream_t stream);
 void noise_fill_host(bool mol, int B, int C, int t0, int t1, uint64_t seed, const uint64_t *seg_id, float *out);
+struct NllArgs { const float *logits, *target; const int *seg_len; float *nll; double *sum; int n, T, C; };      // (csrc/wrnn_nll.hip)
+hipError_t launch_nll(bool mol, const NllArgs &a, hipStream_t stream);
+void nll_host(bool mol, const NllArgs &a);
 hipError_t launch_stream(const LoopArgs &args, int mode, hipStream_t stream);
 hipError_t launch_loop(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int loop_max_depth(int mode);
@@ -1114,6 +1117,41 @@ extern "C" int wrnn_noise_fill_host(int mode, int32_t n_segments, int32_t n_clas
     const int rc = check_noise_fill(mode, n_segments, n_classes, t_begin, t_end, out);
     if (rc != WRNN_OK) return rc;
     noise_fill_host(mode == WRNN_MODE_MOL, n_segments, n_classes, t_begin, t_end, seed, seg_id, out);
+    return WRNN_OK;
+}
+
+namespace {
+int check_nll(const wrnn_nll_call *c)
+{
+    if (!c) { set_err("NULL wrnn_nll_call"); return WRNN_ERR_ARG; }
+    if (c->struct_bytes != sizeof(wrnn_nll_call)) { set_err("wrnn_nll_call.struct_bytes is %u, this library's struct has %zu bytes", c->struct_bytes, sizeof(wrnn_nll_call)); return WRNN_ERR_ARG; }
+    if (!c->logits || !c->target || !c->sum) { set_err("NULL %s", !c->logits ? "logits" : !c->target ? "target" : "sum"); return WRNN_ERR_ARG; }
+    if (c->mode != WRNN_MODE_MOL && c->mode != WRNN_MODE_RAW) { set_err("unknown mode %d", c->mode); return WRNN_ERR_ARG; }
+    if (c->mode == WRNN_MODE_MOL && c->n_classes != 30) { set_err("MOL scores 30 outputs per step (10 mixtures), not %d", c->n_classes); return WRNN_ERR_ARG; }
+    if (c->mode == WRNN_MODE_RAW && (c->n_classes < 2 || c->n_classes > 2048)) { set_err("RAW scores 2..2048 classes, not %d", c->n_classes); return WRNN_ERR_ARG; }
+    if (c->n_segments < 1 || c->T < 1) { set_err("bad shape: %d segments, %d steps", c->n_segments, c->T); return WRNN_ERR_ARG; }
+    return WRNN_OK;
+}
+NllArgs nll_args(const wrnn_nll_call *c) { return NllArgs{c->logits, c->target, c->seg_len, c->nll, c->sum, c->n_segments, c->T, c->n_classes}; }
+}  // namespace
+
+extern "C" int wrnn_nll(int device, const wrnn_nll_call *c)
+{
+    const int rc = check_nll(c);
+    if (rc != WRNN_OK) return rc;
+    const int cus = wrnn_device_cus(device);
+    if (cus < 0) return cus;
+    DeviceGuard dg(device);
+    HIPCHK(dg.err);
+    HIPCHK(launch_nll(c->mode == WRNN_MODE_MOL, nll_args(c), (hipStream_t)c->stream));
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_nll_host(const wrnn_nll_call *c)
+{
+    const int rc = check_nll(c);
+    if (rc != WRNN_OK) return rc;
+    nll_host(c->mode == WRNN_MODE_MOL, nll_args(c));
     return WRNN_OK;
 }
 

@@ -177,6 +177,9 @@ class WaveRNN(nn.Module):
         self.post_algo = 'native'
         #: upper bound on the sampling noise resident at once (bytes); longer runs draw it slice by slice
         self.noise_chunk_bytes = 2 << 30          # (round 6: 2 GB, was 128 MB -- every slice boundary is a relaunch of the loop kernel behind a draw; 9-bit RAW on 256 segments: 48 -> 9 launches, 369.8 -> 351.0 ms per pass, profiles/r06br_noise_chunk.log)
+        #: score() / batch.score_corpus(): upper bound on the logits one scoring call keeps resident (T * n * n_classes * 4 bytes); a longer utterance
+        #: list is scored chunk by chunk.  A setting like `noise_chunk_bytes`, not a measurement
+        self.score_logits_bytes = 8 << 30
         #: optional `f(steps_done, T, n_segments, seconds)` called after every noise slice of generate() (row a17: the
         #: reference's gen_display read-out, :241/:267-271); None = silent, no extra synchronisation
         self.progress_callback = None
@@ -398,6 +401,14 @@ class WaveRNN(nn.Module):
             out = eng.run(mels_up, aux, B, T, stride, noise, self.hop_length, algo=algo, out=out,
                           t_range=None if (t0 == 0 and t1 == T) else (t0, t1), progress=prog, sparse_groups=sparse_groups)
         return out
+
+    def score(self, mels, wav, mu_law=None, per_step=False):
+        """Teacher-forced negative log-likelihood of one utterance: what the reference's `forward` (:131-167) and its training loss
+        (train_wavernn.py:83, :123) give `wav` under this model, on the loop kernels (score.py).  mels (1, feat, N) as for `generate`; wav a float
+        array in [-1, 1] (an integer array: labels).  min(len(wav), N * hop) steps count.  Returns dict(nll_sum, steps, nll_mean -- nats per sample --,
+        bits_per_sample [, per_step])."""
+        from .score import score
+        return score(self, mels, wav, mu_law=mu_law, per_step=per_step)
 
     def gen_display(self, i, seq_len, b_size, gen_rate):
         """The reference's progress line (:267-271; utils/display.py:9-18 `progbar` + `stream`), for use as

@@ -196,3 +196,29 @@ def wavernn_pruner(model, start_prune, prune_steps, target_sparsity=0.95, prune_
     if hasattr(model, 'invalidate_engines'):
         pruner.on_change = model.invalidate_engines
     return pruner, layers
+
+
+def score_at_sparsities(model, mels, wavs, sparsities, linear=False, block=(16, 1), mu_law=None):
+    """The corpus score of `model` (a `wavernn_amd.WaveRNN` on a HIP device) after block-pruning it to each of `sparsities`: for every value the
+    weights are pruned with `block_prune_state_dict` (`linear`: fc1 / fc2 too), loaded into a COPY of the model and scored with
+    `batch.score_corpus` on the copy's `loop_algo` -- `auto` runs a qualifying MoL pack on wrnn_sparse_kernel, so the score comes from the kernel
+    that would generate the audio.  Returns [(sparsity, nll_mean over all counted steps, the loop kernel that ran)]; the caller's model keeps its
+    weights and its device packs."""
+    import copy
+    import torch
+    from .batch import score_corpus
+    sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items() if k in GRU_KEYS + LINEAR_KEYS}
+    out = []
+    for z in sparsities:
+        pruned, _ = block_prune_state_dict(sd, float(z), block, linear=linear)
+        engines = (model._engine, model._pre)          # device handles: not copied -- the copy builds its own packs
+        model._engine = model._pre = None
+        try:
+            m = copy.deepcopy(model)
+        finally:
+            model._engine, model._pre = engines
+        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pruned.items()}, strict=False)
+        res = score_corpus(m, mels, wavs, mu_law=mu_law)
+        out.append((float(z), sum(r['nll_sum'] for r in res) / sum(r['steps'] for r in res), m.last_loop_kernel))
+        del m
+    return out

@@ -83,6 +83,33 @@ def random_mel(seed, n_frames, n_mels=80):
     return np.random.RandomState(seed).uniform(0.0, 1.0, size=(n_mels, n_frames)).astype(np.float32)
 
 
+def score_loss_inputs(kind, seed=4100, n=16):
+    """Seeded inputs of the loss fixtures (tests/golden/score_loss_cases.npz: the reference's results on them; the logits themselves are rebuilt
+    from the seed, the legacy `RandomState` streams are frozen): (logits [T][n][C] float32, labels [n][T] int64) in the layouts `wrnn_nll` reads.
+    kind 'mol': T = 400; labels on the 16-bit grid, one in 30 at or next to -1 (0 / 16: -1 and -0.9995) and one in 30 at or next to +1; log-scales
+    U[-9, 1], means within two scales of the target 2 label / 65535 - 1, mixture logits N(0, 3^2).  kind 'raw512' / 'raw256': T = 64, logits
+    N(0, 4^2), uniform labels with 0 and C - 1 among them."""
+    rs = np.random.RandomState(seed + (0 if kind == 'mol' else int(kind[3:])))
+    if kind == 'mol':
+        T, edge = 400, 16
+        lab = rs.randint(0, 65536, size=(n, T))
+        u = rs.random_sample((n, T))
+        lo = np.where(rs.random_sample((n, T)) < 0.5, 0, edge)
+        hi = 65535 - np.where(rs.random_sample((n, T)) < 0.5, 0, edge)
+        lab = np.where(u < 1 / 30, lo, np.where(u < 2 / 30, hi, lab)).astype(np.int64)
+        y = np.float32(2) * lab.astype(np.float32) / np.float32(65535) - np.float32(1)
+        log_scales = rs.uniform(-9, 1, size=(n, T, 10))
+        means = y[..., None].astype(np.float64) + rs.uniform(-2, 2, size=(n, T, 10)) * np.exp(log_scales)
+        mix = rs.normal(0, 3, size=(n, T, 10))
+        logits = np.concatenate([mix, means, log_scales], axis=2).astype(np.float32)
+    else:
+        C, T = int(kind[3:]), 64
+        logits = rs.normal(0, 4, size=(n, T, C)).astype(np.float32)
+        lab = rs.randint(0, C, size=(n, T)).astype(np.int64)
+        lab[0, 0], lab[0, 1] = 0, C - 1
+    return np.ascontiguousarray(logits.transpose(1, 0, 2)), lab
+
+
 def random_tacotron_state_dict(seed, shapes):
     """Seeded random-init Tacotron state dict from a (key, shape, dtype) table (tests/golden/tacotron_shapes.json, written by
     scripts/make_golden.py from the reference's module): Xavier-uniform matrices like `Tacotron.init_model` (models/tacotron.py:
