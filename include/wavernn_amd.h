@@ -527,6 +527,39 @@ size_t wrnn_taco_batch_workspace_bytes(int32_t n_sent);
  * and the limit).  wrnn_taco_status reads this workspace as it reads wrnn_taco_decode's. */
 int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c);
 
+/*
+ * The TEACHER-FORCED decoder loop for a list of sentences: ground-truth-aligned (GTA) mels, the reference's `Tacotron.forward(x, m,
+ * generate_gta=True)` (models/tacotron.py:310-368) at batch size 1 per sentence, in eval mode.  The PreNet input of decoder step k is column
+ * k r - 1 of the sentence's own ground-truth mel `force_mel[s]` (the zero <GO> frame for k = 0), so a small pre-pass (wrnn_taco_prenet_kernel)
+ * forms the PreNet output of every step of every sentence into the workspace, and the loop (wrnn_taco_batch_kernel<SMAX, true>) is the batched
+ * kernel's step without the mel poll, the stop test and the two PreNet layers: eight exchange hops per step, not ten.  Sentence s runs exactly
+ * steps_s = ceil(frames[s] / r) steps (there is no stop test) and writes steps_s rows of mel_out[s] / scores_out[s]; rows past them are not
+ * touched.  Every sentence is decoded as if alone: its output does not depend on what rides along, and is bit-identical to the free-running
+ * kernel's wherever the forced mel equals that kernel's own output.  Limits: those of wrnn_taco_decode_batch (1..WRNN_TACO_BATCH_MAX sentences
+ * of 1..WRNN_TACO_BATCH_NMAX encoder positions, r <= 8, >= 128 CUs, else WRNN_ERR_RESIDENCY), 1..2^20 frames per sentence.  The arrays
+ * marked HOST are read during the call only.
+ */
+typedef struct wrnn_taco_forced_call {
+    uint32_t struct_bytes;
+    int32_t n_sent;                    /* 1..WRNN_TACO_BATCH_MAX */
+    int32_t r, max_r;                  /* as wrnn_taco_call */
+    const int32_t *n;                  /* HOST [n_sent]: encoder positions, 1..WRNN_TACO_BATCH_NMAX */
+    const int32_t *frames;             /* HOST [n_sent]: N_s >= 1 ground-truth frames; steps_s = ceil(N_s / r) */
+    const float *const *seq, *const *seq_proj;   /* HOST [n_sent] of DEVICE [n_s][256] */
+    const float *const *force_mel;     /* HOST [n_sent] of DEVICE [n_mels][N_s], the decoder's scale ([-4, 4]) */
+    float *const *mel_out;             /* HOST [n_sent] of DEVICE [steps_s][n_mels][r] */
+    float *const *scores_out;          /* HOST [n_sent] of DEVICE [steps_s][n_s] */
+    void *workspace;                   /* wrnn_taco_forced_workspace_bytes(n_sent, frames, r) */
+    size_t workspace_bytes;
+    void *stream;
+} wrnn_taco_forced_call;
+/* The batched decoder's prefix and tagged vectors, then the PreNet table (128 floats per step).  0 for a bad table: n_sent outside
+ * 1..WRNN_TACO_BATCH_MAX, frames NULL or outside 1..2^20, r outside 1..8. */
+size_t wrnn_taco_forced_workspace_bytes(int32_t n_sent, const int32_t *frames, int32_t r);
+/* Asynchronous on `stream` (the pre-pass launch, then the cooperative launch).  Every argument is validated before the device is touched
+ * (WRNN_ERR_ARG; wrnn_taco_last_error() names the sentence and the limit).  wrnn_taco_status reads this workspace as it reads the others'. */
+int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c);
+
 /* The bidirectional GRU that ends a CBHG (reference models/tacotron.py:95, applied at :137: `x, _ = self.rnn(x)`), one sequence,
  * hidden size 128 (encoder and post-net of the reference's hparams): one persistent workgroup per direction with W_hh in
  * registers.  gi_* = W_ih x + b_ih for all frames (a plain GEMM: the caller's).  Errors: wrnn_taco_last_error(). */

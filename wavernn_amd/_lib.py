@@ -31,7 +31,7 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
            'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch',
            'wrnn_bigru_many', 'wrnn_taco_front_workspace_bytes_many', 'wrnn_taco_encode_many', 'wrnn_taco_postnet_many',
-           'wrnn_taco_front_debug_host_handle']
+           'wrnn_taco_front_debug_host_handle', 'wrnn_taco_forced_workspace_bytes', 'wrnn_taco_decode_forced']
 
 
 class Weights(ctypes.Structure):
@@ -84,6 +84,16 @@ class TacoBatchCall(ctypes.Structure):
                 ('seq', ctypes.POINTER(ctypes.c_void_p)), ('seq_proj', ctypes.POINTER(ctypes.c_void_p)),
                 ('mel_out', ctypes.POINTER(ctypes.c_void_p)), ('scores_out', ctypes.POINTER(ctypes.c_void_p)),
                 ('steps_done', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t), ('stream', ctypes.c_void_p)]
+
+
+class TacoForcedCall(ctypes.Structure):
+    """wrnn_taco_forced_call: n / frames / seq / seq_proj / force_mel / mel_out / scores_out point to HOST arrays of n_sent entries."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32), ('n_sent', ctypes.c_int32), ('r', ctypes.c_int32), ('max_r', ctypes.c_int32),
+                ('n', ctypes.POINTER(ctypes.c_int32)), ('frames', ctypes.POINTER(ctypes.c_int32)),
+                ('seq', ctypes.POINTER(ctypes.c_void_p)), ('seq_proj', ctypes.POINTER(ctypes.c_void_p)),
+                ('force_mel', ctypes.POINTER(ctypes.c_void_p)), ('mel_out', ctypes.POINTER(ctypes.c_void_p)),
+                ('scores_out', ctypes.POINTER(ctypes.c_void_p)), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('stream', ctypes.c_void_p)]
 
 
 class BigruCall(ctypes.Structure):
@@ -272,6 +282,9 @@ def lib():
     L.wrnn_taco_batch_workspace_bytes.argtypes = [ctypes.c_int32]
     L.wrnn_taco_batch_workspace_bytes.restype = ctypes.c_size_t
     L.wrnn_taco_decode_batch.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoBatchCall)]
+    L.wrnn_taco_forced_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
+    L.wrnn_taco_forced_workspace_bytes.restype = ctypes.c_size_t
+    L.wrnn_taco_decode_forced.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoForcedCall)]
     L.wrnn_bigru.argtypes = [ctypes.c_int, ctypes.POINTER(BigruCall)]
     L.wrnn_taco_front_create.argtypes = [ctypes.POINTER(TacoFrontWeights), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_taco_front_destroy.argtypes = [ctypes.c_void_p]

@@ -25,6 +25,22 @@
 // every step.  (tests/test_taco_batch_exchange_model.py checks the protocol, the ends included, under adversarial timing.)
 // Spins: a poll waits at most for the slowest workgroup's layer of eight sentences (tens of microseconds); SPIN_LIMIT iterations of a sleep
 // and up to eight reloads are seconds.
+//
+// FORCED (the second template parameter; `wrnn_taco_decode_forced`): the teacher-forced form of the same step, for ground-truth-aligned mels
+// (the reference's `Tacotron.forward(x, m, generate_gta=True)`, models/tacotron.py:310-368).  The PreNet's input of step k is column k r - 1 of the
+// recording's own mel (<GO> for k = 0), known before the loop: wrnn_taco_prenet_kernel forms pre2[s][k][0..128) for every step of every
+// sentence into a table in the workspace (the same row ownership, lane split, butterfly and fmaxf(x + b, 0) as L1 / L2 below: the same bits), and
+// the loop starts at L3, which stages its PreNet half from that table with plain loads (the table is immutable while the loop runs).  There
+// is no poll of the previous mel block, no stop test, no L1 / L2 and no PreNet weight registers; sentence s is live for exactly
+// max_steps[s] = ceil(frames[s] / r) steps; the mel rows go to mel_out[s] only (nobody reads BV_MEL).  L3 .. L10 are the code below, unchanged.
+// WAR safety of the parity buffers WITHOUT the mel poll: an entry of step t (buffer t & 1) is overwritten by a store of step t + 2, and its last
+// reader is a staging of step t + 1 (the `ptag` polls of L3, L8, L9).  A wave stores for step t + 2 only after its workgroup has passed the
+// L9 and L10 polls of step t + 1 (X2 and X3: 512 entries each, one per wave of the grid), and a wave publishes X2 / X3 of step t + 1 in L8 / L9
+// only after its own workgroup's stagings of that layer and of every earlier one -- which include every read of a step-t entry (the latest:
+// H2(t), staged in L9 of step t + 1 before X3(t + 1) is published, and no step-(t + 2) store precedes its workgroup's L10 poll of X3(t + 1)).
+// Every wave publishes an LSTM unit of every live sentence in every step and every workgroup polls all of them, so the argument covers every
+// workgroup and every live sentence; an ended sentence is neither stored nor polled.  (tests/test_taco_forced_exchange_model.py runs this
+// order under adversarial timing; one buffer per vector fails there.)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -63,6 +79,13 @@ struct TacoBatchArgs {
     int n_sent, r, max_r;
     float stop_threshold;
 };
+// the forced form: + the PreNet table of the pre-pass, [pre_off[s] + step][T_P2] for sentence s
+struct TacoForcedArgs : TacoBatchArgs {
+    const float *pre2;
+    int pre_off[B_SMAX];
+};
+template <bool FORCED> struct TacoArgsOf { typedef TacoBatchArgs type; };
+template <> struct TacoArgsOf<true> { typedef TacoForcedArgs type; };
 
 // a value that is the same in every lane, moved to a scalar register
 __device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
@@ -72,11 +95,11 @@ __device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float,
 // x + sigm(o) * tanh(c) here and not there.
 #pragma clang fp contract(off)
 
-template <int SMAX>
-__global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchArgs a)
+template <int SMAX, bool FORCED = false>
+__global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const typename TacoArgsOf<FORCED>::type a)
 {
     __shared__ __attribute__((aligned(16))) float xb[SMAX][2][1024];  // a layer's input vector(s); layers alternate the two buffers
-    __shared__ __attribute__((aligned(16))) float melv[SMAX][BL_MEL]; // the previous step's mel block (stop test + prenet input)
+    __shared__ __attribute__((aligned(16))) float melv[FORCED ? 1 : SMAX][BL_MEL]; // the previous step's mel block (stop test + prenet input)
     __shared__ __attribute__((aligned(16))) float ahv[SMAX][T_DD];    // attn_h of this step (query layer and rnn_input)
     __shared__ __attribute__((aligned(16))) float sc[SMAX][B_NMAX];   // scores of the step (raw, then normalised)
     __shared__ __attribute__((aligned(16))) float att[SMAX][B_NMAX];  // this workgroup's copy of the previous attention ...
@@ -114,8 +137,8 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
 #define LD_V() ldw4(a.w.attn_v_w + k0, true)
 #define LD_LB() ldw4(a.w.attn_L_b + k0, true)
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 w_fc1 = LEAN ? z4 : LD_FC1();
-    const float4 w_fc2 = LEAN ? z4 : LD_FC2();
+    const float4 w_fc1 = (LEAN || FORCED) ? z4 : LD_FC1();              // (FORCED: the PreNet ran in the pre-pass)
+    const float4 w_fc2 = (LEAN || FORCED) ? z4 : LD_FC2();
     float4 g_i[3][2], g_h[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -170,7 +193,8 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
     for (int k = tid; k < T_AF * 2 * T_AK; k += NT) convT[(k % (2 * T_AK)) * T_AF + k / (2 * T_AK)] = a.w.attn_conv_w[k];
     for (int k = tid; k < T_DD * T_AF; k += NT) LT[(k % T_AF) * T_DD + k / T_AF] = a.w.attn_L_w[k];
     for (int k = tid; k < SMAX * 2 * 1024; k += NT) (&xb[0][0][0])[k] = 0.f;
-    for (int k = tid; k < SMAX * BL_MEL; k += NT) (&melv[0][0])[k] = 0.f;
+    if constexpr (!FORCED)
+        for (int k = tid; k < SMAX * BL_MEL; k += NT) (&melv[0][0])[k] = 0.f;
     for (int k = tid; k < SMAX * B_NMAX; k += NT) { (&sc[0][0])[k] = 0.f; (&att[0][0])[k] = 0.f; (&cum[0][0])[k] = 0.f; (&ahv[0][0])[k] = 0.f; }
     if (tid < 4) misc[tid] = 0;
     __syncthreads();
@@ -237,7 +261,13 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
         for (int s = 0; s < SMAX; ++s)
             if (LV(s) && step >= a.s[s].max_steps) { live &= ~(1u << s); dn[s] = step; }
         if (live == 0u) break;
-        const float4 wfc1 = LEAN ? LD_FC1() : w_fc1;
+        // (FORCED: L3 is the first staging of a step and writes xb[.][1], which the slower waves may still be reading in L10 of the step
+        // before; the free-running form has the mel poll's barrier in between)
+        if constexpr (FORCED) __syncthreads();
+        // (wfc1 / wfc2 are declared at the step's scope, outside the `if constexpr` blocks: declared inside one, their lifetime ends at its brace
+        // and the free-running instantiations allocate registers differently -- 3 to 22 more SGPR spills -- than before the FORCED parameter)
+        const float4 wfc1 = (LEAN && !FORCED) ? LD_FC1() : w_fc1;
+      if constexpr (!FORCED) {
         if (step > 0) poll_in(&melv[0][0], BL_MEL, BV_MEL + (p ^ 1) * BL_MEL, nmel, FIXED(nmel), ptag, 1);
         STAGED();
         {
@@ -276,8 +306,10 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
             for (int s = 0; s < SMAX; ++s)
                 if (LV(s)) pub(s, BV_PRE1 + p * T_P1 + gw, fmaxf(t1[s] + b_fc1, 0.f), tag);
         }
+      }
         // ---- L2: PreNet fc2 ----
-        const float4 wfc2 = LEAN ? LD_FC2() : w_fc2;
+        const float4 wfc2 = (LEAN && !FORCED) ? LD_FC2() : w_fc2;
+      if constexpr (!FORCED) {
         poll_in(&xb[0][0][0], 2048, BV_PRE1 + p * T_P1, T_P1, FIXED(T_P1), tag, 2);
         STAGED();
         if (u128) {
@@ -288,6 +320,7 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
             for (int s = 0; s < SMAX; ++s)
                 if (LV(s)) pub(s, BV_PRE2 + p * T_P2 + gw, fmaxf(t2[s] + b_fc2, 0.f), tag);
         }
+      }
         // ---- L3: attention GRUCell on [context(t-1), prenet] with h = attn_h(t-1) (:233-235) ----
         float4 gi1[3];
 #pragma unroll
@@ -296,7 +329,16 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
             poll_in(&xb[0][1][0], 2048, BV_CTX + (p ^ 1) * T_DD, T_DD, FIXED(T_DD), ptag, 3);
             poll_in(&xb[0][1][512], 2048, BV_ATTNH + (p ^ 1) * T_DD, T_DD, FIXED(T_DD), ptag, 3);
         }
-        poll_in(&xb[0][1][T_DD], 2048, BV_PRE2 + p * T_P2, T_P2, FIXED(T_P2), tag, 3);
+        if constexpr (FORCED) {                                       // the PreNet half: this step's row of the pre-pass table (plain loads)
+            float pv[SMAX];
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s) pv[s] = (LV(s) && tid < T_P2) ? a.pre2[((size_t)a.pre_off[s] + (size_t)step) * T_P2 + tid] : 0.f;
+#pragma unroll
+            for (int s = 0; s < SMAX; ++s)
+                if (LV(s) && tid < T_P2) xb[s][1][T_DD + tid] = pv[s];
+        } else {
+            poll_in(&xb[0][1][T_DD], 2048, BV_PRE2 + p * T_P2, T_P2, FIXED(T_P2), tag, 3);
+        }
         STAGED();
         if (u256) {
 #pragma unroll
@@ -507,7 +549,7 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
             for (int s = 0; s < SMAX; ++s)
                 if (LV(s)) {
                     if (lane == 0) a.s[s].mel_out[(size_t)step * nmel + gw] = t10[s];
-                    pub(s, BV_MEL + p * BL_MEL + gw, t10[s], tag);
+                    if constexpr (!FORCED) pub(s, BV_MEL + p * BL_MEL + gw, t10[s], tag);
                 }
         }
         for (int q = gw + R_NWV; q < nmel; q += R_NWV) {              // r >= 7 only: the rows past the 512 resident ones, from L2
@@ -518,15 +560,17 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
                 const float x = wave_total(fma4(wb, xb[s][1] + 256 + k0, fma4(wa, xb[s][1] + k0, 0.f)));
                 if (LV(s)) {
                     if (lane == 0) a.s[s].mel_out[(size_t)step * nmel + q] = x;
-                    pub(s, BV_MEL + p * BL_MEL + q, x, tag);
+                    if constexpr (!FORCED) pub(s, BV_MEL + p * BL_MEL + q, x, tag);
                 }
             }
         }
     }
-    if (gt == 0) {
+    if constexpr (!FORCED) {
+        if (gt == 0) {
 #pragma unroll
-        for (int s = 0; s < SMAX; ++s)
-            if (s < a.n_sent) a.steps_done[s] = dn[s];
+            for (int s = 0; s < SMAX; ++s)
+                if (s < a.n_sent) a.steps_done[s] = dn[s];
+        }
     }
 #undef STAGED
 #undef FIXED
@@ -538,6 +582,73 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const TacoBatchA
 #undef LD_MP
 #undef LD_V
 #undef LD_LB
+}
+
+// ---------------- the PreNet pre-pass of the forced form ----------------
+// pre2[off_s + k][0..128) = PreNet(column k r - 1 of sentence s's forced mel; zeros for k = 0), for every step k of every sentence, before the
+// loop.  One workgroup forms PN_CH consecutive steps of one sentence: fc1 into LDS, fc2 from LDS -- no exchange.  The arithmetic is L1 / L2 of
+// wrnn_taco_batch_kernel: a wave owns a row, lane l holds its columns 4 l .. 4 l + 3 (ldw4), four fmaf in that order from 0 (fma4; the lanes
+// past the 80 mel channels contribute 0), wave_total, fmaxf(x + b, 0) -- the bits the loop would have formed from the same input.  The PN_CH
+// steps are independent instruction streams over one read of the row (as the sentences are in the loop kernel).
+constexpr int PN_CH = 8;
+struct TacoPrenetSent {
+    const float *mel;                     // [n_mels][frames]
+    int frames, steps, off, wg0;          // steps = ceil(frames / r); first table row; first workgroup of the sentence
+};
+struct TacoPrenetArgs {
+    const float *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+    TacoPrenetSent s[B_SMAX];
+    float *pre2;
+    int n_sent, r;
+};
+
+__global__ __launch_bounds__(NT) void wrnn_taco_prenet_kernel(const TacoPrenetArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float xin[PN_CH][T_NM];
+    __shared__ __attribute__((aligned(16))) float p1[PN_CH][T_P1];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int si = 0;
+    for (int i = 1; i < B_SMAX; ++i)
+        if (i < a.n_sent && (int)blockIdx.x >= a.s[i].wg0) si = i;
+    const TacoPrenetSent sn = a.s[si];
+    const int kf = ((int)blockIdx.x - sn.wg0) * PN_CH;                 // first step of this workgroup
+    const int cnt = sn.steps - kf < PN_CH ? sn.steps - kf : PN_CH;
+    for (int q = tid; q < PN_CH * T_NM; q += NT) {
+        const int c = q / T_NM, m = q % T_NM, k = kf + c;
+        xin[c][m] = (c < cnt && k > 0) ? sn.mel[(size_t)m * sn.frames + ((size_t)k * a.r - 1)] : 0.f;      // k r - 1 <= frames - 1 for k < steps
+    }
+    __syncthreads();
+    const int k0 = 4 * lane;
+    float4 wr = ldw4(a.fc1_w + (size_t)w * T_NM + k0, k0 < T_NM);
+    for (int row = w; row < T_P1; row += NW) {
+        const float4 wn = ldw4(a.fc1_w + (size_t)(row + NW) * T_NM + k0, row + NW < T_P1 && k0 < T_NM);      // the next row, in flight under this one
+        const float b = a.fc1_b[row];
+        float t[PN_CH];
+#pragma unroll
+        for (int c = 0; c < PN_CH; ++c) {
+            float x = 0.f;
+            if (k0 < T_NM) x = fma4(wr, xin[c] + k0, 0.f);
+            t[c] = wave_total(x);
+        }
+#pragma unroll
+        for (int c = 0; c < PN_CH; ++c)
+            if (lane == c) p1[c][row] = fmaxf(t[c] + b, 0.f);
+        wr = wn;
+    }
+    __syncthreads();
+    wr = ldw4(a.fc2_w + (size_t)w * T_P1 + k0, true);
+    for (int row = w; row < T_P2; row += NW) {
+        const float4 wn = ldw4(a.fc2_w + (size_t)(row + NW) * T_P1 + k0, row + NW < T_P2);
+        const float b = a.fc2_b[row];
+        float t[PN_CH];
+#pragma unroll
+        for (int c = 0; c < PN_CH; ++c) t[c] = wave_total(fma4(wr, p1[c] + k0, 0.f));
+#pragma unroll
+        for (int c = 0; c < PN_CH; ++c)
+            if (lane == c && c < cnt) a.pre2[((size_t)sn.off + kf + c) * T_P2 + row] = fmaxf(t[c] + b, 0.f);
+        wr = wn;
+    }
 }
 
 }  // namespace wrnn
@@ -629,6 +740,113 @@ extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, co
     void *params[] = {(void *)&a};
     const void *kern = c->n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2> : c->n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4>
                                                                                                    : (const void *)wrnn_taco_batch_kernel<8>;
+    e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
+    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
+    return WRNN_OK;
+}
+
+// ---------------- the forced form: ground-truth-aligned mels ----------------
+constexpr int32_t FORCED_MAX_FRAMES = 1 << 20;
+
+// workspace: [the batched decoder's prefix | tagged vectors of n_sent sentences | the PreNet table, (sum of steps) rows of T_P2 floats]
+extern "C" size_t wrnn_taco_forced_workspace_bytes(int32_t n_sent, const int32_t *frames, int32_t r)
+{
+    if (n_sent < 1 || n_sent > B_SMAX || !frames || r < 1 || r > R_MAXR) return 0;
+    size_t steps = 0;
+    for (int s = 0; s < n_sent; ++s) {
+        if (frames[s] < 1 || frames[s] > FORCED_MAX_FRAMES) return 0;
+        steps += (size_t)((frames[s] + r - 1) / r);
+    }
+    return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8 + steps * T_P2 * 4;
+}
+
+extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
+{
+    // ---- arguments: everything is checked before the first HIP call ----
+    if (!w || !c) { taco_err("null argument"); return WRNN_ERR_ARG; }
+    if (c->struct_bytes != sizeof(wrnn_taco_forced_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
+        taco_err("struct size mismatch (header / library versions differ)");
+        return WRNN_ERR_ARG;
+    }
+    if (c->n_sent < 1 || c->n_sent > B_SMAX) {
+        taco_err("n_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", c->n_sent, B_SMAX);
+        return WRNN_ERR_ARG;
+    }
+    if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
+        taco_err("r=%d max_r=%d: frames per step must be 1..min(max_r, %d)", c->r, c->max_r, R_MAXR);
+        return WRNN_ERR_ARG;
+    }
+    if (!c->n || !c->frames || !c->seq || !c->seq_proj || !c->force_mel || !c->mel_out || !c->scores_out || !c->workspace) {
+        taco_err("null buffer: n, frames, seq, seq_proj, force_mel, mel_out, scores_out and workspace are all required");
+        return WRNN_ERR_ARG;
+    }
+    for (int s = 0; s < c->n_sent; ++s) {
+        if (c->n[s] < 1 || c->n[s] > B_NMAX) {
+            taco_err("sentence %d: n=%d encoder positions, the forced kernel takes 1..%d (WRNN_TACO_BATCH_NMAX)", s, c->n[s], B_NMAX);
+            return WRNN_ERR_ARG;
+        }
+        if (c->frames[s] < 1 || c->frames[s] > FORCED_MAX_FRAMES) {
+            taco_err("sentence %d: frames=%d ground-truth frames, 1..%d", s, c->frames[s], FORCED_MAX_FRAMES);
+            return WRNN_ERR_ARG;
+        }
+        if (!c->seq[s] || !c->seq_proj[s] || !c->force_mel[s] || !c->mel_out[s] || !c->scores_out[s]) {
+            taco_err("sentence %d: null buffer (seq, seq_proj, force_mel, mel_out and scores_out are required)", s);
+            return WRNN_ERR_ARG;
+        }
+    }
+    const size_t need = wrnn_taco_forced_workspace_bytes(c->n_sent, c->frames, c->r);
+    if (c->workspace_bytes < need) {
+        taco_err("workspace of %zu bytes, these %d sentences need %zu (wrnn_taco_forced_workspace_bytes)", c->workspace_bytes, c->n_sent, need);
+        return WRNN_ERR_ARG;
+    }
+    if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
+        w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
+        taco_err("unsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)");
+        return WRNN_ERR_ARG;
+    }
+    // ---- device ----
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if (prop.multiProcessorCount < R_NWG) {
+        taco_err("the forced decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
+                 prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
+    TacoForcedArgs a;
+    TacoPrenetArgs pa;
+    memset(&a, 0, sizeof a);
+    memset(&pa, 0, sizeof pa);
+    a.w = *w;
+    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
+    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
+    float *pre2 = reinterpret_cast<float *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES + (size_t)c->n_sent * BV_END * 8);
+    a.pre2 = pre2; pa.pre2 = pre2;
+    int off = 0, wgs = 0;
+    for (int s = 0; s < c->n_sent; ++s) {
+        const int steps = (c->frames[s] + c->r - 1) / c->r;
+        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
+        a.s[s].n = c->n[s]; a.s[s].max_steps = steps;
+        a.pre_off[s] = off;
+        pa.s[s].mel = c->force_mel[s]; pa.s[s].frames = c->frames[s]; pa.s[s].steps = steps; pa.s[s].off = off; pa.s[s].wg0 = wgs;
+        off += steps;                                                  // (<= 8 * 2^20)
+        wgs += (steps + PN_CH - 1) / PN_CH;
+    }
+    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
+    pa.fc1_w = w->prenet_fc1_w; pa.fc1_b = w->prenet_fc1_b; pa.fc2_w = w->prenet_fc2_w; pa.fc2_b = w->prenet_fc2_b;
+    pa.n_sent = c->n_sent; pa.r = c->r;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
+    e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
+    if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    hipLaunchKernelGGL(wrnn_taco_prenet_kernel, dim3(wgs), dim3(NT), 0, stream, pa);
+    e = hipGetLastError();
+    if (e != hipSuccess) { taco_err("launch of the PreNet pre-pass (%d workgroups): %s", wgs, hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    void *params[] = {(void *)&a};
+    const void *kern = c->n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2, true> : c->n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4, true>
+                                                                                                         : (const void *)wrnn_taco_batch_kernel<8, true>;
     e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
     if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
     return WRNN_OK;

@@ -3,7 +3,11 @@ to a corpus (score.py): what the reference's validation would report with its tr
 
 DIR/<id>.npy mels (80, N) in [0, 1] are paired by <id> with DIR/<id>.npy (a float waveform in [-1, 1], or integer labels as preprocess.py writes
 them) or DIR/<id>.wav (16-bit PCM) audio ALREADY at the model's sample rate -- nothing is resampled.  One line per utterance, then the corpus mean
-over all counted samples."""
+over all counted samples.
+
+The reference trains its vocoder on ground-truth-aligned mels, not on the recordings' own: `--mels DATA/gta --wavs DATA/quant` (DATA/gta as
+`python -m wavernn_amd.gta_tacotron --tts_weights T.pyt --path DATA` or the reference's `train_tacotron.py --force_gta` writes it) scores the vocoder
+against what it was trained on."""
 import argparse
 from pathlib import Path
 

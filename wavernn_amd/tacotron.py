@@ -12,6 +12,9 @@ bidirectional GRUs as `wrnn_bigru`; the eager loop stays as the any-device form.
 the encoder and the post-net -- embedding, pre-net, both CBHGs, `encoder_proj`, `post_proj` -- as HIP kernels through the C ABI
 (`wrnn_taco_encode` / `wrnn_taco_postnet`, csrc/wrnn_cbhg.hip), so that the whole Tacotron side is behind include/wavernn_amd.h.
 `generate_batch(list_of_ids)` decodes up to eight sentences per pass of the decoder kernel (`wrnn_taco_decode_batch`, csrc/wrnn_taco_batch.hip).
+`forward_gta(ids, mel)` / `forward_gta_batch(...)` run the decoder TEACHER-FORCED over a recording's own mel -- the reference's
+`Tacotron.forward(x, m, generate_gta=True)` (:310-368), the ground-truth-aligned features its vocoder is trained on -- through
+`wrnn_taco_decode_forced` (the same file; `python -m wavernn_amd.gta_tacotron` is the command line).
 
     tts = TacotronInference(state_dict, device='cuda')
     _, m, attn = tts.generate(ids, steps=800)                 # same returns as the reference: (80, N), (fft, N), (N, chars); the
@@ -58,6 +61,7 @@ class TacotronInference:
         self._front_ws = None                      # its workspace, reused and grown
         self._dec_w = None                         # generate_batch: (wrnn_taco_weights, the tensors it points to), built once
         self._batch_ws = None                      # ... and the workspace of wrnn_taco_decode_batch, reused and grown
+        self._forced_ws = None                     # forward_gta: the workspace of wrnn_taco_decode_forced, reused and grown
 
     def _count(self, pattern):
         n = 0
@@ -551,6 +555,181 @@ class TacotronInference:
         out = []
         for i, e in enumerate(encs):
             mel, attn = decoded[i] if decoded[i] is not None else self._decode_kernel(e[0], e[1], steps)
+            linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+            out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
+        return out
+
+    # -- ground-truth-aligned mels: the teacher-forced decoder ------------------------------------------------------------------
+    def _forced_mel(self, mel):
+        """A ground-truth mel (n_mels, N) or (1, n_mels, N), numpy or tensor -> contiguous float32 (n_mels, N) on the device."""
+        m = torch.as_tensor(np.asarray(mel) if not torch.is_tensor(mel) else mel).to(self.device, torch.float32)
+        m = m.reshape(self.n_mels, -1).contiguous()
+        if m.size(1) < 1:
+            raise ValueError('a ground-truth mel needs at least one frame')
+        return m
+
+    def _decode_forced_eager(self, seq, seq_proj, m):
+        """The teacher-forced loop of `Tacotron.forward(x, m, generate_gta=True)` (:347-354) over `_decoder_step`, on any device: decoder step k
+        reads column k r - 1 of `m` (n_mels, N), the <GO> frame at k = 0; ceil(N / r) steps, no stop test.  Returns (mel (1, n_mels, steps r),
+        attention (steps, n)) device tensors."""
+        dev, n = self.device, seq.size(1)
+        z = lambda *s: torch.zeros(*s, device=dev)
+        st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
+                  c2=z(1, self.lstm_dims), context=z(1, self.decoder_dims), cumulative=z(1, n), attention=z(1, n))
+        frames, scores = [], []
+        for t in range(0, m.size(1), self.r):
+            prenet_in = m[:, t - 1].unsqueeze(0) if t > 0 else z(1, self.n_mels)
+            m_, s_ = self._decoder_step(seq, seq_proj, prenet_in, st)
+            frames.append(m_)
+            scores.append(s_.clone())
+        return torch.cat(frames, dim=2), torch.cat(scores, 0)
+
+    def _decode_forced_kernel(self, encs, mels):
+        """The teacher-forced decoder loops of up to `_lib.TACO_BATCH_MAX` sentences in ONE `wrnn_taco_decode_forced` call (the PreNet pre-pass
+        and the forced form of the batched persistent kernel, csrc/wrnn_taco_batch.hip).  encs: [(seq (1, n, 256), seq_proj (1, n, 256))], every
+        n <= `_lib.TACO_BATCH_NMAX`; mels: [(n_mels, N_s) float32 device tensors].  Returns [(mel (1, n_mels, steps_s r), attention (steps_s,
+        n_s))] device tensors.  Fails loudly without the extension or a HIP device -- there is no host fallback."""
+        import ctypes
+        from . import _lib
+        dev = self.device
+        if dev.type != 'cuda':
+            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
+        L, S, r = _lib.lib(), len(encs), self.r
+        seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
+        projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
+        mels = [m.contiguous() for m in mels]
+        steps = [(m.size(1) + r - 1) // r for m in mels]
+        outs = [torch.zeros(k, self.n_mels, r, device=dev) for k in steps]
+        scores = [torch.zeros(k, q.size(0), device=dev) for k, q in zip(steps, seqs)]
+        frames = (ctypes.c_int32 * S)(*[m.size(1) for m in mels])
+        need = int(L.wrnn_taco_forced_workspace_bytes(S, frames, r))
+        if need == 0:
+            raise ValueError(f'{S} sentences of {list(frames)} frames at r={r}: 1..{_lib.TACO_BATCH_MAX} sentences of 1..2^20 frames per call')
+        if self._forced_ws is None or self._forced_ws.numel() < need:
+            self._forced_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._forced_ws
+        c = _lib.TacoForcedCall()
+        c.struct_bytes = ctypes.sizeof(_lib.TacoForcedCall)
+        c.n_sent, c.r, c.max_r = S, r, self.max_r
+        c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
+        c.frames = frames
+        for name, ts in (('seq', seqs), ('seq_proj', projs), ('force_mel', mels), ('mel_out', outs), ('scores_out', scores)):
+            setattr(c, name, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
+        c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+        c.stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = L.wrnn_taco_decode_forced((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(self.decoder_weights()),
+                                       ctypes.byref(c))
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'wrnn_taco_decode_forced failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        st4 = (ctypes.c_uint32 * 4)()
+        rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
+        if rc != _lib.WRNN_OK or st4[0] != 0:
+            raise _lib.WrnnError(f'Tacotron forced decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
+        return [(m.permute(1, 0, 2).reshape(1, self.n_mels, k * r), a) for m, a, k in zip(outs, scores, steps)]
+
+    @staticmethod
+    def _gta_groups(steps, max_batch):
+        """Groups of at most `max_batch` sentence indices, sentences sorted by their step count first (a stable sort), so that the sentences of
+        one kernel end close to each other."""
+        order = sorted(range(len(steps)), key=lambda i: steps[i])
+        return [order[g:g + max_batch] for g in range(0, len(order), max_batch)]
+
+    @torch.no_grad()
+    def forward_gta(self, ids, mel, kernel=False, cbhg_kernel=False):
+        """Ground-truth-aligned (GTA) features of one utterance: the reference's `Tacotron.forward(x, m, generate_gta=True)` (:310-368) at batch
+        size 1 -- the decoder run TEACHER-FORCED over the recording's own mel `mel` (n_mels, N) on the decoder's scale ([-4, 4]): step k reads
+        column k r - 1 of it (the <GO> frame at k = 0), steps = ceil(N / r), no stop test.  Returns numpy (gta (n_mels, steps r), linear (fft,
+        steps r), attention (steps, n_chars)) -- the reference's three returns.
+
+        kernel=False: the eager loop over `_decoder_step`, on any device.  kernel=True (HIP device): `wrnn_taco_decode_forced` -- a PreNet
+        pre-pass over all steps and the forced form of the batched persistent kernel (csrc/wrnn_taco_batch.hip) -- for sentences of at most
+        `_lib.TACO_BATCH_NMAX` ids; cbhg_kernel as in `generate()`.
+
+        Two deliberate differences from the reference's `train_tacotron.py --force_gta`.  MODE: `create_gta_features` (:178-199) calls
+        `model(x, mels)` WITHOUT generate_gta, so the checked-in script runs in train mode (PreNet dropout, batch statistics in the batch
+        norms); this is the eval form the signature offers, the only deterministic one.  PADDING: the reference pads a batch's texts with zeros
+        and attends over the padding, so an utterance's features depend on its batch companions; here every sentence is decoded as if alone
+        (the reference at batch size 1)."""
+        dev = self.device
+        if cbhg_kernel and dev.type != 'cuda':
+            from . import _lib
+            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
+        self._bigru_kernel = bool(kernel) and dev.type == 'cuda'
+        front = bool(cbhg_kernel) and self._front_handle() is not None
+        self.last_front_path = 'hip' if front else 'torch'
+        m = self._forced_mel(mel)
+        seq, seq_proj = self.encode_kernel(ids)[:2] if front else self.encode(ids)
+        if kernel:
+            from . import _lib
+            if seq.size(1) > _lib.TACO_BATCH_NMAX:
+                raise ValueError(f'{seq.size(1)} ids: the forced kernel takes sentences of at most {_lib.TACO_BATCH_NMAX} (kernel=False, or forward_gta_batch)')
+            gta, attn = self._decode_forced_kernel([(seq, seq_proj)], [m])[0]
+        else:
+            gta, attn = self._decode_forced_eager(seq, seq_proj, m)
+        if front:
+            linear = self.postnet_kernel(gta)[0].transpose(0, 1)
+        else:
+            linear = F.linear(self._cbhg(gta, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+        return gta[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()
+
+    @torch.no_grad()
+    def forward_gta_batch(self, list_of_ids, list_of_mels, kernel=True, cbhg_kernel=False, max_batch=8):
+        """`forward_gta()` for a list of utterances: a list of (gta, linear, attention), one per utterance in the caller's order, as
+        `forward_gta()` returns them (see there for the two deliberate differences from the reference's script: eval mode, and every sentence
+        decoded as if alone -- the result does not depend on what rides along).
+
+        kernel=True (HIP device): the sentences are sorted by their step count and decoded in groups of at most `max_batch` (1..8) through
+        `wrnn_taco_decode_forced`, one persistent kernel per group, so a group's ragged ends waste little.  A sentence of more than
+        `_lib.TACO_BATCH_NMAX` (256) ids goes through the EAGER loop on the device: there is no single-sentence forced kernel.
+        cbhg_kernel=True: `encode_kernel_many` / `postnet_kernel_many` over all sentences (64 per call) and ONE transfer at the end, exactly as
+        `generate_batch` does; otherwise the encoder and the post-net run per sentence on the torch ops.  kernel=False: a loop of
+        `forward_gta(kernel=False)`, on any device."""
+        from . import _lib
+        if len(list_of_ids) != len(list_of_mels):
+            raise ValueError(f'{len(list_of_ids)} id lists for {len(list_of_mels)} mels')
+        if not kernel:
+            return [self.forward_gta(ids, mel, kernel=False, cbhg_kernel=cbhg_kernel) for ids, mel in zip(list_of_ids, list_of_mels)]
+        if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
+            raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
+        dev = self.device
+        if cbhg_kernel and dev.type != 'cuda':
+            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
+        self._bigru_kernel = dev.type == 'cuda'
+        front = bool(cbhg_kernel) and self._front_handle() is not None
+        self.last_front_path = 'hip' if front else 'torch'
+        M = _lib.TACO_FRONT_MANY_MAX
+        ms = [self._forced_mel(mel) for mel in list_of_mels]
+        if front:
+            enc_many = lambda chunk: self.encode_kernel_many(chunk) if len(chunk) > 1 else [self.encode_kernel(chunk[0])]
+            post_many = lambda chunk: self.postnet_kernel_many(chunk) if len(chunk) > 1 else [self.postnet_kernel(chunk[0])]
+            encs = [e[:2] for c in range(0, len(list_of_ids), M) for e in enc_many(list_of_ids[c:c + M])]
+        else:
+            encs = [self.encode(ids) for ids in list_of_ids]
+        decoded = [None] * len(encs)
+        short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
+        steps = [(ms[i].size(1) + self.r - 1) // self.r for i in short]
+        for group in self._gta_groups(steps, int(max_batch)):
+            idx = [short[j] for j in group]
+            for i, d in zip(idx, self._decode_forced_kernel([encs[i] for i in idx], [ms[i] for i in idx])):
+                decoded[i] = d
+        for i, e in enumerate(encs):
+            if decoded[i] is None:                                                 # more than 256 ids: the eager loop on the device
+                decoded[i] = self._decode_forced_eager(e[0], e[1], ms[i])
+        if front:
+            mels = [d[0] for d in decoded]
+            lins = [l for c in range(0, len(mels), M) for l, _ in post_many(mels[c:c + M])]
+            parts = [t.reshape(-1) for (mel, attn), lin in zip(decoded, lins) for t in (mel[0], lin, attn)]
+            flat = torch.cat(parts).cpu().numpy() if parts else None
+            out, o = [], 0
+            for (mel, attn), lin in zip(decoded, lins):
+                trio = []
+                for t in (mel[0], lin, attn):
+                    trio.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
+                    o += t.numel()
+                out.append((trio[0], trio[1].T, trio[2]))
+            return out
+        out = []
+        for mel, attn in decoded:
             linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
             out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
         return out
