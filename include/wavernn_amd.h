@@ -676,6 +676,29 @@ int wrnn_selftest(int device, int which);
 /* microseconds per all-gather round measured by the last wrnn_selftest(device, 2) (<0 if none) */
 float wrnn_selftest_metric(void);
 
+/*
+ * TWO sentence groups per launch of the batched Tacotron decoder (appended to ABI v9: the symbols tell whether a library has them).  The
+ * kernel of wrnn_taco_decode_batch / wrnn_taco_decode_forced is a grid of 128 workgroups, one per CU; a device of 256 CUs runs a second,
+ * fully independent group of up to WRNN_TACO_BATCH_MAX sentences on its other 128 workgroups in the SAME cooperative launch (the GROUPED
+ * instantiations of wrnn_taco_batch_kernel: 256 workgroups; a workgroup finds its group and its index within it from its block index).
+ * calls[g] is an ordinary call struct with a workspace of its own (wrnn_taco_batch_workspace_bytes / wrnn_taco_forced_workspace_bytes of that
+ * group); the groups share the weights and nothing else -- no exchange word, no barrier -- and a group's workgroups return when their own group
+ * has no live sentence.  Every sentence's mel_out, scores_out and steps_done are BIT-IDENTICAL to the plain call on its group alone; rows past a
+ * sentence's end are not touched; wrnn_taco_status reads each group's workspace separately.  n_groups == 1 IS the plain call.  For
+ * n_groups == 2 every argument of every group is validated before the device is touched: the plain call's checks (the message prefixed
+ * "group g: "), and WRNN_ERR_ARG for n_groups outside 1..WRNN_TACO_GROUPS_MAX, a NULL calls / calls[g], groups whose stream, r or max_r
+ * differ, and workspaces whose byte ranges overlap.  WRNN_ERR_RESIDENCY on a device with fewer than 256 CUs, or one that cannot hold 256
+ * workgroups of the kernel at once (asked before anything is enqueued: neither workspace has been written; decode the groups by two plain
+ * calls).  Asynchronous on the stream, no allocation, no synchronisation: per group the memset of its status words and tags (forced: and its
+ * PreNet pre-pass launch), then ONE cooperative launch.
+ */
+#define WRNN_TACO_GROUPS_MAX 2
+int wrnn_taco_decode_batch_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *const *calls, int32_t n_groups);
+int wrnn_taco_decode_forced_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *const *calls, int32_t n_groups);
+/* Test hook: the grouped kernel's map of a block index 0..255 to (group 0..1, workgroup 0..127 within the group).  Returns the placement the
+ * library was built with (0: contiguous halves; 1: interleaved, a group on four XCDs), -1 for a block outside the grid or a NULL output. */
+int wrnn_debug_taco_group_of(int32_t block, int32_t *group, int32_t *local);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,8 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
            'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch',
            'wrnn_bigru_many', 'wrnn_taco_front_workspace_bytes_many', 'wrnn_taco_encode_many', 'wrnn_taco_postnet_many',
-           'wrnn_taco_front_debug_host_handle', 'wrnn_taco_forced_workspace_bytes', 'wrnn_taco_decode_forced']
+           'wrnn_taco_front_debug_host_handle', 'wrnn_taco_forced_workspace_bytes', 'wrnn_taco_decode_forced',
+           'wrnn_taco_decode_batch_groups', 'wrnn_taco_decode_forced_groups', 'wrnn_debug_taco_group_of']
 
 
 class Weights(ctypes.Structure):
@@ -75,6 +76,7 @@ class TacoCall(ctypes.Structure):
 
 TACO_BATCH_MAX = 8           # WRNN_TACO_BATCH_MAX: sentences per wrnn_taco_decode_batch call
 TACO_BATCH_NMAX = 256        # WRNN_TACO_BATCH_NMAX: encoder positions per sentence in that call
+TACO_GROUPS_MAX = 2          # WRNN_TACO_GROUPS_MAX: sentence groups per wrnn_taco_decode_batch_groups / wrnn_taco_decode_forced_groups call
 
 
 class TacoBatchCall(ctypes.Structure):
@@ -285,6 +287,9 @@ def lib():
     L.wrnn_taco_forced_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
     L.wrnn_taco_forced_workspace_bytes.restype = ctypes.c_size_t
     L.wrnn_taco_decode_forced.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoForcedCall)]
+    L.wrnn_taco_decode_batch_groups.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(ctypes.POINTER(TacoBatchCall)), ctypes.c_int32]
+    L.wrnn_taco_decode_forced_groups.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(ctypes.POINTER(TacoForcedCall)), ctypes.c_int32]
+    L.wrnn_debug_taco_group_of.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.wrnn_bigru.argtypes = [ctypes.c_int, ctypes.POINTER(BigruCall)]
     L.wrnn_taco_front_create.argtypes = [ctypes.POINTER(TacoFrontWeights), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.wrnn_taco_front_destroy.argtypes = [ctypes.c_void_p]

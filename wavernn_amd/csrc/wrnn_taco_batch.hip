@@ -87,6 +87,43 @@ struct TacoForcedArgs : TacoBatchArgs {
 template <bool FORCED> struct TacoArgsOf { typedef TacoBatchArgs type; };
 template <> struct TacoArgsOf<true> { typedef TacoForcedArgs type; };
 
+// ---------------- two groups per launch (`wrnn_taco_decode_batch_groups` / `wrnn_taco_decode_forced_groups`) ----------------
+// The grouped launch has G_MAX * R_NWG workgroups: each group of R_NWG workgroups runs the step code below on an argument block of its own --
+// sentence table, status words, tagged vectors, steps_done, r, threshold, PreNet table -- and shares nothing with the other group but the
+// (read-only) weight tensors.  Nothing in this kernel waits for the whole grid: every wait is a poll of a tagged entry of the workgroup's own
+// group, so a group's workgroups return when their group has no live sentence, however long the other one runs.
+constexpr int G_MAX = WRNN_TACO_GROUPS_MAX;
+static_assert(G_MAX == 2, "taco_group_of maps onto two groups");
+template <bool FORCED> struct TacoGroupArgs { typename TacoArgsOf<FORCED>::type g[G_MAX]; };
+template <bool FORCED, bool GROUPED> struct TacoKernArgsOf { typedef typename TacoArgsOf<FORCED>::type type; };
+template <bool FORCED> struct TacoKernArgsOf<FORCED, true> { typedef TacoGroupArgs<FORCED> type; };
+
+// Where the workgroups of a group sit (a speed question only: nothing below depends on where a workgroup runs).
+//   0: contiguous halves -- group = block / 128.  Under the round-robin dispatch over the eight XCDs each group has 16 workgroups on every XCD.
+//   1: interleaved -- group = bit 2 of (block mod 8): under that dispatch group 0 keeps to XCDs 0-3 and group 1 to XCDs 4-7, 32 workgroups each,
+//      so a group's exchange stays within four XCDs.
+// (DESIGN.md section 6 "Two sentence groups per launch" has the measurement behind the shipped value.)
+#ifndef WRNN_TACO_GROUP_PLACEMENT
+#define WRNN_TACO_GROUP_PLACEMENT 1
+#endif
+static_assert(WRNN_TACO_GROUP_PLACEMENT == 0 || WRNN_TACO_GROUP_PLACEMENT == 1, "placement 0 (contiguous) or 1 (interleaved)");
+// block 0 .. G_MAX * R_NWG - 1 -> (group, local workgroup 0 .. R_NWG - 1): a bijection for either placement
+__host__ __device__ __forceinline__ void taco_group_of(int block, int &group, int &local)
+{
+    if constexpr (WRNN_TACO_GROUP_PLACEMENT == 0) {
+        group = block / R_NWG;
+        local = block % R_NWG;
+    } else {
+        group = (block >> 2) & 1;
+        local = (block >> 3) * 4 + (block & 3);
+    }
+}
+template <bool GROUPED, class KA> __device__ __forceinline__ const auto &taco_group_args(const KA &ka, int group)
+{
+    if constexpr (GROUPED) return ka.g[group];
+    else return ka;
+}
+
 // a value that is the same in every lane, moved to a scalar register
 __device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
@@ -95,9 +132,14 @@ __device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float,
 // x + sigm(o) * tanh(c) here and not there.
 #pragma clang fp contract(off)
 
-template <int SMAX, bool FORCED = false>
-__global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const typename TacoArgsOf<FORCED>::type a)
+template <int SMAX, bool FORCED = false, bool GROUPED = false>
+__global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const typename TacoKernArgsOf<FORCED, GROUPED>::type ka)
 {
+    // GROUPED: this workgroup's group and its index within it; everything below knows the group only through `a` and `wg`
+    int grp = 0, lwg = (int)blockIdx.x;
+    if constexpr (GROUPED) taco_group_of((int)blockIdx.x, grp, lwg);
+    const typename TacoArgsOf<FORCED>::type &a = taco_group_args<GROUPED>(ka, grp);
+
     __shared__ __attribute__((aligned(16))) float xb[SMAX][2][1024];  // a layer's input vector(s); layers alternate the two buffers
     __shared__ __attribute__((aligned(16))) float melv[FORCED ? 1 : SMAX][BL_MEL]; // the previous step's mel block (stop test + prenet input)
     __shared__ __attribute__((aligned(16))) float ahv[SMAX][T_DD];    // attn_h of this step (query layer and rnn_input)
@@ -113,7 +155,7 @@ __global__ __launch_bounds__(NT, 1) void wrnn_taco_batch_kernel(const typename T
     // ranges are free at that point of a step and are re-staged before they are read again.  NOT xb[s][.][512 ...): the recurrent halves of the
     // GRU / LSTM inputs are not polled at step 0 and must still hold the zeros of the initial state.)
 
-    const int tid = threadIdx.x, lane = tid & 63, wg = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wg = lwg;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);           // (scalar: the wave's rows, biases and cell states stay out of the vector registers)
     const int gw = wg * NW + w;
     const int gt = wg * NT + tid, NGT = R_NWG * NT;
@@ -666,50 +708,76 @@ extern "C" size_t wrnn_taco_batch_workspace_bytes(int32_t n_sent)
     return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8;
 }
 
-extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
+// The argument checks of a free-running call: everything is checked before the first HIP call.  `pre` is "" (wrnn_taco_decode_batch) or
+// "group g: " (wrnn_taco_decode_batch_groups) in front of the message.
+static int check_batch_call(const wrnn_taco_weights *w, const wrnn_taco_batch_call *c, const char *pre)
 {
-    // ---- arguments: everything is checked before the first HIP call ----
-    if (!w || !c) { taco_err("null argument"); return WRNN_ERR_ARG; }
+    if (!w || !c) { taco_err("%snull argument", pre); return WRNN_ERR_ARG; }
     if (c->struct_bytes != sizeof(wrnn_taco_batch_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
-        taco_err("struct size mismatch (header / library versions differ)");
+        taco_err("%sstruct size mismatch (header / library versions differ)", pre);
         return WRNN_ERR_ARG;
     }
     if (c->n_sent < 1 || c->n_sent > B_SMAX) {
-        taco_err("n_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", c->n_sent, B_SMAX);
+        taco_err("%sn_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", pre, c->n_sent, B_SMAX);
         return WRNN_ERR_ARG;
     }
     if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
-        taco_err("r=%d max_r=%d: frames per step must be 1..min(max_r, %d)", c->r, c->max_r, R_MAXR);
+        taco_err("%sr=%d max_r=%d: frames per step must be 1..min(max_r, %d)", pre, c->r, c->max_r, R_MAXR);
         return WRNN_ERR_ARG;
     }
     if (!c->n || !c->max_steps || !c->seq || !c->seq_proj || !c->mel_out || !c->scores_out || !c->steps_done || !c->workspace) {
-        taco_err("null buffer: n, max_steps, seq, seq_proj, mel_out, scores_out, steps_done and workspace are all required");
+        taco_err("%snull buffer: n, max_steps, seq, seq_proj, mel_out, scores_out, steps_done and workspace are all required", pre);
         return WRNN_ERR_ARG;
     }
     for (int s = 0; s < c->n_sent; ++s) {
         if (c->n[s] < 1 || c->n[s] > B_NMAX) {
-            taco_err("sentence %d: n=%d encoder positions, the batched kernel takes 1..%d (WRNN_TACO_BATCH_NMAX; longer: wrnn_taco_decode)", s, c->n[s], B_NMAX);
+            taco_err("%ssentence %d: n=%d encoder positions, the batched kernel takes 1..%d (WRNN_TACO_BATCH_NMAX; longer: wrnn_taco_decode)", pre, s,
+                     c->n[s], B_NMAX);
             return WRNN_ERR_ARG;
         }
         if (c->max_steps[s] < 1) {
-            taco_err("sentence %d: max_steps=%d, at least 1", s, c->max_steps[s]);
+            taco_err("%ssentence %d: max_steps=%d, at least 1", pre, s, c->max_steps[s]);
             return WRNN_ERR_ARG;
         }
         if (!c->seq[s] || !c->seq_proj[s] || !c->mel_out[s] || !c->scores_out[s]) {
-            taco_err("sentence %d: null buffer (seq, seq_proj, mel_out and scores_out are required)", s);
+            taco_err("%ssentence %d: null buffer (seq, seq_proj, mel_out and scores_out are required)", pre, s);
             return WRNN_ERR_ARG;
         }
     }
     if (c->workspace_bytes < wrnn_taco_batch_workspace_bytes(c->n_sent)) {
-        taco_err("workspace of %zu bytes, %d sentences need %zu (wrnn_taco_batch_workspace_bytes)", c->workspace_bytes, c->n_sent,
+        taco_err("%sworkspace of %zu bytes, %d sentences need %zu (wrnn_taco_batch_workspace_bytes)", pre, c->workspace_bytes, c->n_sent,
                  wrnn_taco_batch_workspace_bytes(c->n_sent));
         return WRNN_ERR_ARG;
     }
     if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
         w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
-        taco_err("unsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)");
+        taco_err("%sunsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)", pre);
         return WRNN_ERR_ARG;
     }
+    return WRNN_OK;
+}
+
+// the kernel's argument block of a checked call
+static void fill_batch_args(TacoBatchArgs &a, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
+{
+    memset(&a, 0, sizeof a);
+    a.w = *w;
+    for (int s = 0; s < c->n_sent; ++s) {
+        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
+        a.s[s].n = c->n[s]; a.s[s].max_steps = c->max_steps[s];
+    }
+    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
+    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
+    a.steps_done = c->steps_done;
+    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
+    a.stop_threshold = c->stop_threshold;
+}
+
+extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
+{
+    // ---- arguments: everything is checked before the first HIP call ----
+    const int bad = check_batch_call(w, c, "");
+    if (bad != WRNN_OK) return bad;
     // ---- device ----
     DeviceGuard dg(device);
     hipError_t e = dg.err;
@@ -723,17 +791,7 @@ extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, co
         return WRNN_ERR_RESIDENCY;
     }
     TacoBatchArgs a;
-    memset(&a, 0, sizeof a);
-    a.w = *w;
-    for (int s = 0; s < c->n_sent; ++s) {
-        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
-        a.s[s].n = c->n[s]; a.s[s].max_steps = c->max_steps[s];
-    }
-    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
-    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
-    a.steps_done = c->steps_done;
-    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
-    a.stop_threshold = c->stop_threshold;
+    fill_batch_args(a, w, c);
     hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
     e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
     if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
@@ -760,64 +818,56 @@ extern "C" size_t wrnn_taco_forced_workspace_bytes(int32_t n_sent, const int32_t
     return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8 + steps * T_P2 * 4;
 }
 
-extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
+// The argument checks of a forced call, as check_batch_call.
+static int check_forced_call(const wrnn_taco_weights *w, const wrnn_taco_forced_call *c, const char *pre)
 {
-    // ---- arguments: everything is checked before the first HIP call ----
-    if (!w || !c) { taco_err("null argument"); return WRNN_ERR_ARG; }
+    if (!w || !c) { taco_err("%snull argument", pre); return WRNN_ERR_ARG; }
     if (c->struct_bytes != sizeof(wrnn_taco_forced_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
-        taco_err("struct size mismatch (header / library versions differ)");
+        taco_err("%sstruct size mismatch (header / library versions differ)", pre);
         return WRNN_ERR_ARG;
     }
     if (c->n_sent < 1 || c->n_sent > B_SMAX) {
-        taco_err("n_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", c->n_sent, B_SMAX);
+        taco_err("%sn_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", pre, c->n_sent, B_SMAX);
         return WRNN_ERR_ARG;
     }
     if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
-        taco_err("r=%d max_r=%d: frames per step must be 1..min(max_r, %d)", c->r, c->max_r, R_MAXR);
+        taco_err("%sr=%d max_r=%d: frames per step must be 1..min(max_r, %d)", pre, c->r, c->max_r, R_MAXR);
         return WRNN_ERR_ARG;
     }
     if (!c->n || !c->frames || !c->seq || !c->seq_proj || !c->force_mel || !c->mel_out || !c->scores_out || !c->workspace) {
-        taco_err("null buffer: n, frames, seq, seq_proj, force_mel, mel_out, scores_out and workspace are all required");
+        taco_err("%snull buffer: n, frames, seq, seq_proj, force_mel, mel_out, scores_out and workspace are all required", pre);
         return WRNN_ERR_ARG;
     }
     for (int s = 0; s < c->n_sent; ++s) {
         if (c->n[s] < 1 || c->n[s] > B_NMAX) {
-            taco_err("sentence %d: n=%d encoder positions, the forced kernel takes 1..%d (WRNN_TACO_BATCH_NMAX)", s, c->n[s], B_NMAX);
+            taco_err("%ssentence %d: n=%d encoder positions, the forced kernel takes 1..%d (WRNN_TACO_BATCH_NMAX)", pre, s, c->n[s], B_NMAX);
             return WRNN_ERR_ARG;
         }
         if (c->frames[s] < 1 || c->frames[s] > FORCED_MAX_FRAMES) {
-            taco_err("sentence %d: frames=%d ground-truth frames, 1..%d", s, c->frames[s], FORCED_MAX_FRAMES);
+            taco_err("%ssentence %d: frames=%d ground-truth frames, 1..%d", pre, s, c->frames[s], FORCED_MAX_FRAMES);
             return WRNN_ERR_ARG;
         }
         if (!c->seq[s] || !c->seq_proj[s] || !c->force_mel[s] || !c->mel_out[s] || !c->scores_out[s]) {
-            taco_err("sentence %d: null buffer (seq, seq_proj, force_mel, mel_out and scores_out are required)", s);
+            taco_err("%ssentence %d: null buffer (seq, seq_proj, force_mel, mel_out and scores_out are required)", pre, s);
             return WRNN_ERR_ARG;
         }
     }
     const size_t need = wrnn_taco_forced_workspace_bytes(c->n_sent, c->frames, c->r);
     if (c->workspace_bytes < need) {
-        taco_err("workspace of %zu bytes, these %d sentences need %zu (wrnn_taco_forced_workspace_bytes)", c->workspace_bytes, c->n_sent, need);
+        taco_err("%sworkspace of %zu bytes, these %d sentences need %zu (wrnn_taco_forced_workspace_bytes)", pre, c->workspace_bytes, c->n_sent, need);
         return WRNN_ERR_ARG;
     }
     if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
         w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
-        taco_err("unsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)");
+        taco_err("%sunsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)", pre);
         return WRNN_ERR_ARG;
     }
-    // ---- device ----
-    DeviceGuard dg(device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    if (prop.multiProcessorCount < R_NWG) {
-        taco_err("the forced decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
-                 prop.multiProcessorCount);
-        return WRNN_ERR_RESIDENCY;
-    }
-    TacoForcedArgs a;
-    TacoPrenetArgs pa;
+    return WRNN_OK;
+}
+
+// the argument blocks of a checked call: the loop's and the pre-pass's; returns the pre-pass's workgroup count
+static int fill_forced_args(TacoForcedArgs &a, TacoPrenetArgs &pa, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
+{
     memset(&a, 0, sizeof a);
     memset(&pa, 0, sizeof pa);
     a.w = *w;
@@ -838,6 +888,29 @@ extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, c
     a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
     pa.fc1_w = w->prenet_fc1_w; pa.fc1_b = w->prenet_fc1_b; pa.fc2_w = w->prenet_fc2_w; pa.fc2_b = w->prenet_fc2_b;
     pa.n_sent = c->n_sent; pa.r = c->r;
+    return wgs;
+}
+
+extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
+{
+    // ---- arguments: everything is checked before the first HIP call ----
+    const int bad = check_forced_call(w, c, "");
+    if (bad != WRNN_OK) return bad;
+    // ---- device ----
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if (prop.multiProcessorCount < R_NWG) {
+        taco_err("the forced decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
+                 prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
+    TacoForcedArgs a;
+    TacoPrenetArgs pa;
+    const int wgs = fill_forced_args(a, pa, w, c);
     hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
     e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
     if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
@@ -849,5 +922,156 @@ extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, c
                                                                                                          : (const void *)wrnn_taco_batch_kernel<8, true>;
     e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
     if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
+    return WRNN_OK;
+}
+
+// ---------------- two groups per launch ----------------
+// calls[0] and calls[1] are ordinary calls with a workspace each; ONE cooperative launch of G_MAX * R_NWG workgroups decodes both (the GROUPED
+// instantiations of wrnn_taco_batch_kernel: group g's R_NWG workgroups run the step code on calls[g]'s argument block).  SMAX comes from the
+// larger group; the smaller group's slots past its n_sent are the slots past n_sent of any call.
+
+extern "C" int wrnn_debug_taco_group_of(int32_t block, int32_t *group, int32_t *local)
+{
+    if (block < 0 || block >= G_MAX * R_NWG || !group || !local) return -1;
+    int g = 0, l = 0;
+    taco_group_of(block, g, l);
+    *group = g; *local = l;
+    return WRNN_TACO_GROUP_PLACEMENT;
+}
+
+// what the groups entry points check before the per-group checks: the count and the table
+template <class Call> static int check_groups_table(const Call *const *calls, int32_t n_groups)
+{
+    if (n_groups < 1 || n_groups > G_MAX) {
+        taco_err("n_groups=%d: a call decodes 1..%d groups (WRNN_TACO_GROUPS_MAX)", n_groups, G_MAX);
+        return WRNN_ERR_ARG;
+    }
+    if (!calls) { taco_err("null argument: calls is a table of n_groups=%d call structs", n_groups); return WRNN_ERR_ARG; }
+    for (int g = 0; g < n_groups; ++g)
+        if (!calls[g]) { taco_err("group %d: null call (calls[0 .. n_groups) are all required)", g); return WRNN_ERR_ARG; }
+    return WRNN_OK;
+}
+
+// ... and after them: what the groups of one launch must share, and what they must not
+template <class Call> static int check_groups_pair(const Call *c0, const Call *c1)
+{
+    if (c0->stream != c1->stream) {
+        taco_err("group 1: stream %p, group 0 has %p: the groups of a call ride ONE launch on one stream", c1->stream, c0->stream);
+        return WRNN_ERR_ARG;
+    }
+    if (c0->r != c1->r || c0->max_r != c1->max_r) {
+        taco_err("group 1: r=%d max_r=%d, group 0 has r=%d max_r=%d: the groups of a call share the weights, so r and max_r are equal", c1->r, c1->max_r,
+                 c0->r, c0->max_r);
+        return WRNN_ERR_ARG;
+    }
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(c0->workspace), b1 = reinterpret_cast<uintptr_t>(c1->workspace);
+    if (b0 < b1 + c1->workspace_bytes && b1 < b0 + c0->workspace_bytes) {
+        taco_err("the workspaces of group 0 (%zu bytes at %p) and group 1 (%zu bytes at %p) overlap: every group needs a workspace of its own",
+                 c0->workspace_bytes, c0->workspace, c1->workspace_bytes, c1->workspace);
+        return WRNN_ERR_ARG;
+    }
+    return WRNN_OK;
+}
+
+template <bool FORCED> static const void *taco_groups_kernel(int n_sent)
+{
+    return n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2, FORCED, true> : n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4, FORCED, true>
+                                                                                             : (const void *)wrnn_taco_batch_kernel<8, FORCED, true>;
+}
+
+// The device's side of a grouped call, before anything is enqueued: G_MAX * R_NWG workgroups of one per CU must be co-resident.  The occupancy
+// query is the one the runtime's cooperative launch repeats, so a refusal is found here, with neither workspace written.
+static int taco_groups_residency(int device, const void *kern)
+{
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if (prop.multiProcessorCount < G_MAX * R_NWG) {
+        taco_err("a launch of %d groups needs >= %d CUs (%d co-resident workgroups per group, one per CU); device has %d", G_MAX, G_MAX * R_NWG, R_NWG,
+                 prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NT, 0);
+    if (e != hipSuccess) { taco_err("hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if ((long long)per_cu * prop.multiProcessorCount < G_MAX * R_NWG) {
+        taco_err("a launch of %d groups needs %d co-resident workgroups; the device holds %d x %d", G_MAX, G_MAX * R_NWG, per_cu, prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_taco_decode_batch_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *const *calls, int32_t n_groups)
+{
+    // ---- arguments: every group's are checked before the first HIP call ----
+    int bad = check_groups_table(calls, n_groups);
+    if (bad != WRNN_OK) return bad;
+    if (n_groups == 1) return wrnn_taco_decode_batch(device, w, calls[0]);
+    for (int g = 0; g < G_MAX; ++g) {
+        char pre[16];
+        snprintf(pre, sizeof pre, "group %d: ", g);
+        bad = check_batch_call(w, calls[g], pre);
+        if (bad != WRNN_OK) return bad;
+    }
+    bad = check_groups_pair(calls[0], calls[1]);
+    if (bad != WRNN_OK) return bad;
+    // ---- device ----
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    const int n_max = calls[0]->n_sent > calls[1]->n_sent ? calls[0]->n_sent : calls[1]->n_sent;
+    const void *kern = taco_groups_kernel<false>(n_max);
+    bad = taco_groups_residency(device, kern);
+    if (bad != WRNN_OK) return bad;
+    TacoGroupArgs<false> ga;
+    for (int g = 0; g < G_MAX; ++g) fill_batch_args(ga.g[g], w, calls[g]);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(calls[0]->stream);
+    for (int g = 0; g < G_MAX; ++g) {
+        e = hipMemsetAsync(ga.g[g].uw, 0, (size_t)U_END * 4 + (size_t)calls[g]->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
+        if (e != hipSuccess) { taco_err("group %d: hipMemsetAsync: %s", g, hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    }
+    void *params[] = {(void *)&ga};
+    e = hipLaunchCooperativeKernel(kern, dim3(G_MAX * R_NWG), dim3(NT), params, 0, stream);
+    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", G_MAX * R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_taco_decode_forced_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *const *calls, int32_t n_groups)
+{
+    // ---- arguments: every group's are checked before the first HIP call ----
+    int bad = check_groups_table(calls, n_groups);
+    if (bad != WRNN_OK) return bad;
+    if (n_groups == 1) return wrnn_taco_decode_forced(device, w, calls[0]);
+    for (int g = 0; g < G_MAX; ++g) {
+        char pre[16];
+        snprintf(pre, sizeof pre, "group %d: ", g);
+        bad = check_forced_call(w, calls[g], pre);
+        if (bad != WRNN_OK) return bad;
+    }
+    bad = check_groups_pair(calls[0], calls[1]);
+    if (bad != WRNN_OK) return bad;
+    // ---- device ----
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    const int n_max = calls[0]->n_sent > calls[1]->n_sent ? calls[0]->n_sent : calls[1]->n_sent;
+    const void *kern = taco_groups_kernel<true>(n_max);
+    bad = taco_groups_residency(device, kern);
+    if (bad != WRNN_OK) return bad;
+    TacoGroupArgs<true> ga;
+    TacoPrenetArgs pa[G_MAX];
+    int wgs[G_MAX];
+    for (int g = 0; g < G_MAX; ++g) wgs[g] = fill_forced_args(ga.g[g], pa[g], w, calls[g]);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(calls[0]->stream);
+    for (int g = 0; g < G_MAX; ++g) {
+        e = hipMemsetAsync(ga.g[g].uw, 0, (size_t)U_END * 4 + (size_t)calls[g]->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
+        if (e != hipSuccess) { taco_err("group %d: hipMemsetAsync: %s", g, hipGetErrorString(e)); return WRNN_ERR_HIP; }
+        hipLaunchKernelGGL(wrnn_taco_prenet_kernel, dim3(wgs[g]), dim3(NT), 0, stream, pa[g]);        // (one pre-pass launch per group: its table)
+        e = hipGetLastError();
+        if (e != hipSuccess) { taco_err("group %d: launch of the PreNet pre-pass (%d workgroups): %s", g, wgs[g], hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    }
+    void *params[] = {(void *)&ga};
+    e = hipLaunchCooperativeKernel(kern, dim3(G_MAX * R_NWG), dim3(NT), params, 0, stream);
+    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", G_MAX * R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
     return WRNN_OK;
 }

@@ -12,7 +12,8 @@ abbreviation expansion need the reference's text front-end (out of scope).
 (`TacotronInference.generate_batch`, csrc/wrnn_taco_batch.hip), then ONE vocoder pass over all of them (`generate_corpus`, noise drawn inside the
 library under the seeds --seed, --seed + 1, ...).  Same file names.  With --cbhg_kernel the encoder and the post-net of all sentences run side by
 side as well (`wrnn_taco_encode_many` / `wrnn_taco_postnet_many`, one call each per 64 sentences).  Without the flag the per-sentence path runs as
-before."""
+before.  `--groups 2` (with --batch, a device of 256 CUs): two decoder groups of N sentences per launch, one on each half of the device
+(`wrnn_taco_decode_batch_groups`); the same audio."""
 import argparse
 import time
 from pathlib import Path
@@ -40,6 +41,7 @@ def main(argv=None):
     ap.add_argument('--output', default='.', help='output directory')
     ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet; with --batch their _many forms)')
     ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (needs --batched)')
+    ap.add_argument('--groups', type=int, default=1, choices=[1, 2], help='--batch: decoder groups per launch (2: a group on each half of a 256-CU device)')
     ap.add_argument('--seed', type=int, default=0, help='--batch: sentence i draws its sampling noise under seed + i')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
@@ -47,6 +49,8 @@ def main(argv=None):
         ap.error('--batch needs --batched (the one-pass vocoder folds every sentence)')
     if a.batch is not None and not 1 <= a.batch <= 8:
         ap.error('--batch: 1..8 sentences per decoder kernel')
+    if a.groups != 1 and a.batch is None:
+        ap.error('--groups needs --batch')
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     voc = WaveRNN(**SHIPPED, mode=a.mode).to('cuda')
@@ -68,7 +72,7 @@ def main(argv=None):
         from .dsp import save_wav
         print(f'\n| Generating {len(texts)} sentences, {a.batch} per decoder kernel')
         t0 = time.perf_counter()
-        outs = tts.generate_batch([text_to_ids(t) for t in texts], steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel, max_batch=a.batch)
+        outs = tts.generate_batch([text_to_ids(t) for t in texts], steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel, max_batch=a.batch, groups=a.groups)
         t1 = time.perf_counter()
         mels = [torch.tensor(tacotron_to_wavernn_mel(lin)).unsqueeze(0) for _, lin, _ in outs]          # the POSTNET output (:142)
         wavs = generate_corpus(voc, mels, a.target, a.overlap, True, seeds=[a.seed + i for i in range(len(mels))], noise_source='library')

@@ -37,6 +37,7 @@ def main(argv=None):
     ap.add_argument('--path', type=str, required=True, help='the reference\'s data directory: dataset.pkl, text_dict.pkl, mel/<id>.npy')
     ap.add_argument('--out', type=str, default=None, help='output directory (default: <path>/gta)')
     ap.add_argument('--max_batch', type=int, default=8, help='sentences per decoder kernel (1..8)')
+    ap.add_argument('--groups', type=int, default=1, choices=[1, 2], help='decoder groups per launch (2: a group on each half of a 256-CU device)')
     ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too')
     ap.add_argument('--no_kernel', action='store_true', help='the eager loop on any torch device (no HIP kernel)')
     a = ap.parse_args(argv)
@@ -60,7 +61,7 @@ def main(argv=None):
         items = dataset[c:c + CHUNK]
         mels = [np.load(data / 'mel' / f'{item_id}.npy').astype(np.float32) for item_id, _ in items]
         outs = tts.forward_gta_batch([text_to_ids(text_dict[item_id]) for item_id, _ in items], [m * 8 - 4 for m in mels],
-                                     kernel=not a.no_kernel, cbhg_kernel=a.cbhg_kernel, max_batch=a.max_batch)
+                                     kernel=not a.no_kernel, cbhg_kernel=a.cbhg_kernel, max_batch=a.max_batch, groups=a.groups)
         for (item_id, _), m, (_, gta, _) in zip(items, mels, outs):               # `_, gta, _ = model(x, mels)` (:187)
             N = m.shape[1]
             np.save(out_dir / f'{item_id}.npy', ((gta[:, :N] + 4) / 8).astype(np.float32), allow_pickle=False)

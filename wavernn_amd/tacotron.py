@@ -62,6 +62,8 @@ class TacotronInference:
         self._dec_w = None                         # generate_batch: (wrnn_taco_weights, the tensors it points to), built once
         self._batch_ws = None                      # ... and the workspace of wrnn_taco_decode_batch, reused and grown
         self._forced_ws = None                     # forward_gta: the workspace of wrnn_taco_decode_forced, reused and grown
+        self._batch_ws2 = self._forced_ws2 = None  # groups=2: the second group's workspaces of a grouped launch
+        self.last_decode_groups = []               # generate_batch / forward_gta_batch: per native decode call, the sizes of the groups it decoded
 
     def _count(self, pattern):
         n = 0
@@ -462,44 +464,84 @@ class TacotronInference:
         """The decoder loops of up to `_lib.TACO_BATCH_MAX` sentences in ONE persistent kernel (`wrnn_taco_decode_batch`,
         csrc/wrnn_taco_batch.hip).  encs: [(seq (1, n, 256), seq_proj (1, n, 256))], every n <= `_lib.TACO_BATCH_NMAX`.  Returns
         [(mel (1, n_mels, N_s), attention (N_s / r, n_s))] device tensors, each bit-identical to `_decode_kernel(..., variant=2)`."""
+        return self._decode_batch_launch([encs], steps)[0]
+
+    def _decode_batch_launch(self, groups, steps):
+        """The decoder loops of ONE or TWO groups of sentences (each as `_decode_batch_kernel` takes them).  One group: `wrnn_taco_decode_batch`.
+        Two: ONE `wrnn_taco_decode_batch_groups` launch, a group on each half of a 256-CU device, every group with a workspace of its own; where
+        the device refuses the 256 co-resident workgroups (WRNN_ERR_RESIDENCY, nothing written) the two groups take the plain call one after the
+        other.  Returns the groups' results in order; `last_decode_groups` gains one entry per native call."""
         import ctypes
         from . import _lib
         dev = self.device
         if dev.type != 'cuda':
             raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
-        L, S = _lib.lib(), len(encs)
+        L = _lib.lib()
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
         max_steps = (steps + self.r - 1) // self.r
-        seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
-        projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
-        mels = [torch.zeros(max_steps, self.n_mels, self.r, device=dev) for _ in encs]
-        scores = [torch.zeros(max_steps, q.size(0), device=dev) for q in seqs]
-        done = torch.zeros(S, dtype=torch.int32, device=dev)
-        need = int(L.wrnn_taco_batch_workspace_bytes(S))
-        if self._batch_ws is None or self._batch_ws.numel() < need:
-            self._batch_ws = torch.empty(max(need, int(L.wrnn_taco_batch_workspace_bytes(min(_lib.TACO_BATCH_MAX, max(S, 1))))), dtype=torch.uint8, device=dev)
-        ws = self._batch_ws
-        c = _lib.TacoBatchCall()
-        c.struct_bytes = ctypes.sizeof(_lib.TacoBatchCall)
-        c.n_sent, c.r, c.max_r, c.stop_threshold = S, self.r, self.max_r, self.stop_threshold
-        c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
-        c.max_steps = (ctypes.c_int32 * S)(*([max_steps] * S))
-        for name, ts in (('seq', seqs), ('seq_proj', projs), ('mel_out', mels), ('scores_out', scores)):
-            setattr(c, name, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
-        c.steps_done, c.workspace, c.workspace_bytes = done.data_ptr(), ws.data_ptr(), ws.numel()
-        c.stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.wrnn_taco_decode_batch((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(self.decoder_weights()),
-                                      ctypes.byref(c))
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_decode_batch failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        st4 = (ctypes.c_uint32 * 4)()
-        rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
-        if rc != _lib.WRNN_OK or st4[0] != 0:
-            raise _lib.WrnnError(f'Tacotron batched decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
-        ks = [int(k) for k in done.cpu()]
-        return [(m[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * self.r), a[:k]) for m, a, k in zip(mels, scores, ks)]
+        calls = []
+        for slot, encs in enumerate(groups):
+            S = len(encs)
+            seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
+            projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
+            mels = [torch.zeros(max_steps, self.n_mels, self.r, device=dev) for _ in encs]
+            scores = [torch.zeros(max_steps, q.size(0), device=dev) for q in seqs]
+            done = torch.zeros(S, dtype=torch.int32, device=dev)
+            need = int(L.wrnn_taco_batch_workspace_bytes(S))
+            name = '_batch_ws' if slot == 0 else '_batch_ws2'
+            if getattr(self, name) is None or getattr(self, name).numel() < need:
+                setattr(self, name, torch.empty(max(need, int(L.wrnn_taco_batch_workspace_bytes(min(_lib.TACO_BATCH_MAX, max(S, 1))))), dtype=torch.uint8,
+                                                device=dev))
+            ws = getattr(self, name)
+            c = _lib.TacoBatchCall()
+            c.struct_bytes = ctypes.sizeof(_lib.TacoBatchCall)
+            c.n_sent, c.r, c.max_r, c.stop_threshold = S, self.r, self.max_r, self.stop_threshold
+            c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
+            c.max_steps = (ctypes.c_int32 * S)(*([max_steps] * S))
+            for field, ts in (('seq', seqs), ('seq_proj', projs), ('mel_out', mels), ('scores_out', scores)):
+                setattr(c, field, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
+            c.steps_done, c.workspace, c.workspace_bytes = done.data_ptr(), ws.data_ptr(), ws.numel()
+            c.stream = torch.cuda.current_stream(dev).cuda_stream
+            calls.append((c, ws, mels, scores, done, (seqs, projs)))
+
+        def finish(call):
+            c, ws, mels, scores, done, _ = call
+            st4 = (ctypes.c_uint32 * 4)()
+            rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
+            if rc != _lib.WRNN_OK or st4[0] != 0:
+                raise _lib.WrnnError(f'Tacotron batched decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
+            ks = [int(k) for k in done.cpu()]
+            return [(m[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * self.r), a[:k]) for m, a, k in zip(mels, scores, ks)]
+
+        if len(calls) == 2:
+            table = (ctypes.POINTER(_lib.TacoBatchCall) * 2)(*[ctypes.pointer(call[0]) for call in calls])
+            rc = L.wrnn_taco_decode_batch_groups(device, ctypes.byref(self.decoder_weights()), table, 2)
+            if rc == _lib.WRNN_OK:
+                self.last_decode_groups.append(tuple(len(g) for g in groups))
+                return [finish(call) for call in calls]
+            if rc != _lib.ERR_RESIDENCY:
+                raise _lib.WrnnError(f'wrnn_taco_decode_batch_groups failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        elif len(calls) != 1:
+            raise ValueError(f'{len(calls)} groups: a launch decodes 1..{_lib.TACO_GROUPS_MAX}')
+        out = []
+        for call, g in zip(calls, groups):
+            rc = L.wrnn_taco_decode_batch(device, ctypes.byref(self.decoder_weights()), ctypes.byref(call[0]))
+            if rc != _lib.WRNN_OK:
+                raise _lib.WrnnError(f'wrnn_taco_decode_batch failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+            self.last_decode_groups.append((len(g),))
+            out.append(finish(call))
+        return out
+
+    @staticmethod
+    def _pair_groups(groups, n):
+        """The decoder groups of a pass as the launches that decode them: n = 1, one group per launch (the plain call); n = 2, consecutive groups in
+        pairs (one grouped launch each), an odd group out alone.  The order of the groups is kept."""
+        if isinstance(n, bool) or n not in (1, 2):
+            raise ValueError(f'groups={n!r}: 1 (one group of sentences per launch) or 2 (two, on a device of 256 CUs)')
+        return [groups[i:i + n] for i in range(0, len(groups), n)]
 
     @torch.no_grad()
-    def generate_batch(self, list_of_ids, steps=2000, kernel=True, cbhg_kernel=False, max_batch=8):
+    def generate_batch(self, list_of_ids, steps=2000, kernel=True, cbhg_kernel=False, max_batch=8, groups=1):
         """`generate()` for a list of sentences: a list of (mel, linear, attention), one per sentence, as `generate()` returns them.
 
         kernel=True (HIP device): the decoder loops run in groups of at most `max_batch` (1..8) sentences through `wrnn_taco_decode_batch` -- one
@@ -508,12 +550,17 @@ class TacotronInference:
         run per sentence on the torch ops, as in `generate(kernel=True)`.  cbhg_kernel=True: ONE `wrnn_taco_encode_many` call encodes all
         sentences in front of the decoder groups and ONE `wrnn_taco_postnet_many` call runs the post-net over all decoded mels (64 sentences per
         call at most; a call of one sentence takes the single-sentence entry points), each sentence's bits those of `generate(kernel=True,
-        cbhg_kernel=True)`; the results reach the host in one transfer at the end.  kernel=False: a loop of `generate()`, on any device."""
+        cbhg_kernel=True)`; the results reach the host in one transfer at the end.  kernel=False: a loop of `generate()`, on any device.
+
+        groups=2 (opt-in; a device of 256 CUs): consecutive decoder groups ride in pairs on ONE `wrnn_taco_decode_batch_groups` launch, a group on
+        each half of the device -- 2 x `max_batch` sentences per launch, the same bits; an odd group out takes the plain call, and so do both
+        groups of a pair where the device refuses the launch.  `last_decode_groups` lists what ran: per native call, its groups' sizes."""
         from . import _lib
         if not kernel:
             return [self.generate(ids, steps=steps, kernel=False, cbhg_kernel=cbhg_kernel) for ids in list_of_ids]
         if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
             raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
+        self._pair_groups([], groups)                                              # (ValueError for anything but 1 or 2)
         dev = self.device
         if dev.type != 'cuda':
             raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
@@ -531,10 +578,15 @@ class TacotronInference:
             encs = [self.encode(ids) for ids in list_of_ids]
         decoded = [None] * len(encs)
         short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
-        for g in range(0, len(short), int(max_batch)):
-            group = short[g:g + int(max_batch)]
-            for i, d in zip(group, self._decode_batch_kernel([encs[i] for i in group], steps)):
-                decoded[i] = d
+        self.last_decode_groups = []
+        for launch in self._pair_groups([short[g:g + int(max_batch)] for g in range(0, len(short), int(max_batch))], groups):
+            if len(launch) == 1:
+                results = [self._decode_batch_kernel([encs[i] for i in launch[0]], steps)]
+            else:
+                results = self._decode_batch_launch([[encs[i] for i in group] for group in launch], steps)
+            for group, result in zip(launch, results):
+                for i, d in zip(group, result):
+                    decoded[i] = d
         if front:
             for i, e in enumerate(encs):
                 if decoded[i] is None:
@@ -589,43 +641,74 @@ class TacotronInference:
         and the forced form of the batched persistent kernel, csrc/wrnn_taco_batch.hip).  encs: [(seq (1, n, 256), seq_proj (1, n, 256))], every
         n <= `_lib.TACO_BATCH_NMAX`; mels: [(n_mels, N_s) float32 device tensors].  Returns [(mel (1, n_mels, steps_s r), attention (steps_s,
         n_s))] device tensors.  Fails loudly without the extension or a HIP device -- there is no host fallback."""
+        return self._decode_forced_launch([(encs, mels)])[0]
+
+    def _decode_forced_launch(self, groups):
+        """The teacher-forced loops of ONE or TWO groups, each an (encs, mels) pair as `_decode_forced_kernel` takes it.  One group:
+        `wrnn_taco_decode_forced`.  Two: ONE `wrnn_taco_decode_forced_groups` launch (a pre-pass per group, then both loops on the halves of a
+        256-CU device), every group with a workspace of its own; on WRNN_ERR_RESIDENCY (nothing written) the groups take the plain call one
+        after the other.  Returns the groups' results in order; `last_decode_groups` gains one entry per native call."""
         import ctypes
         from . import _lib
         dev = self.device
         if dev.type != 'cuda':
             raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
-        L, S, r = _lib.lib(), len(encs), self.r
-        seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
-        projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
-        mels = [m.contiguous() for m in mels]
-        steps = [(m.size(1) + r - 1) // r for m in mels]
-        outs = [torch.zeros(k, self.n_mels, r, device=dev) for k in steps]
-        scores = [torch.zeros(k, q.size(0), device=dev) for k, q in zip(steps, seqs)]
-        frames = (ctypes.c_int32 * S)(*[m.size(1) for m in mels])
-        need = int(L.wrnn_taco_forced_workspace_bytes(S, frames, r))
-        if need == 0:
-            raise ValueError(f'{S} sentences of {list(frames)} frames at r={r}: 1..{_lib.TACO_BATCH_MAX} sentences of 1..2^20 frames per call')
-        if self._forced_ws is None or self._forced_ws.numel() < need:
-            self._forced_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = self._forced_ws
-        c = _lib.TacoForcedCall()
-        c.struct_bytes = ctypes.sizeof(_lib.TacoForcedCall)
-        c.n_sent, c.r, c.max_r = S, r, self.max_r
-        c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
-        c.frames = frames
-        for name, ts in (('seq', seqs), ('seq_proj', projs), ('force_mel', mels), ('mel_out', outs), ('scores_out', scores)):
-            setattr(c, name, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
-        c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
-        c.stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.wrnn_taco_decode_forced((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(self.decoder_weights()),
-                                       ctypes.byref(c))
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_decode_forced failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        st4 = (ctypes.c_uint32 * 4)()
-        rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
-        if rc != _lib.WRNN_OK or st4[0] != 0:
-            raise _lib.WrnnError(f'Tacotron forced decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
-        return [(m.permute(1, 0, 2).reshape(1, self.n_mels, k * r), a) for m, a, k in zip(outs, scores, steps)]
+        L, r = _lib.lib(), self.r
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        calls = []
+        for slot, (encs, mels) in enumerate(groups):
+            S = len(encs)
+            seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
+            projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
+            mels = [m.contiguous() for m in mels]
+            steps = [(m.size(1) + r - 1) // r for m in mels]
+            outs = [torch.zeros(k, self.n_mels, r, device=dev) for k in steps]
+            scores = [torch.zeros(k, q.size(0), device=dev) for k, q in zip(steps, seqs)]
+            frames = (ctypes.c_int32 * S)(*[m.size(1) for m in mels])
+            need = int(L.wrnn_taco_forced_workspace_bytes(S, frames, r))
+            if need == 0:
+                raise ValueError(f'{S} sentences of {list(frames)} frames at r={r}: 1..{_lib.TACO_BATCH_MAX} sentences of 1..2^20 frames per call')
+            name = '_forced_ws' if slot == 0 else '_forced_ws2'
+            if getattr(self, name) is None or getattr(self, name).numel() < need:
+                setattr(self, name, torch.empty(need, dtype=torch.uint8, device=dev))
+            ws = getattr(self, name)
+            c = _lib.TacoForcedCall()
+            c.struct_bytes = ctypes.sizeof(_lib.TacoForcedCall)
+            c.n_sent, c.r, c.max_r = S, r, self.max_r
+            c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
+            c.frames = frames
+            for field, ts in (('seq', seqs), ('seq_proj', projs), ('force_mel', mels), ('mel_out', outs), ('scores_out', scores)):
+                setattr(c, field, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
+            c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+            c.stream = torch.cuda.current_stream(dev).cuda_stream
+            calls.append((c, ws, outs, scores, steps, (seqs, projs, mels)))
+
+        def finish(call):
+            c, ws, outs, scores, steps, _ = call
+            st4 = (ctypes.c_uint32 * 4)()
+            rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
+            if rc != _lib.WRNN_OK or st4[0] != 0:
+                raise _lib.WrnnError(f'Tacotron forced decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
+            return [(m.permute(1, 0, 2).reshape(1, self.n_mels, k * r), a) for m, a, k in zip(outs, scores, steps)]
+
+        if len(calls) == 2:
+            table = (ctypes.POINTER(_lib.TacoForcedCall) * 2)(*[ctypes.pointer(call[0]) for call in calls])
+            rc = L.wrnn_taco_decode_forced_groups(device, ctypes.byref(self.decoder_weights()), table, 2)
+            if rc == _lib.WRNN_OK:
+                self.last_decode_groups.append(tuple(len(g[0]) for g in groups))
+                return [finish(call) for call in calls]
+            if rc != _lib.ERR_RESIDENCY:
+                raise _lib.WrnnError(f'wrnn_taco_decode_forced_groups failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        elif len(calls) != 1:
+            raise ValueError(f'{len(calls)} groups: a launch decodes 1..{_lib.TACO_GROUPS_MAX}')
+        out = []
+        for call, g in zip(calls, groups):
+            rc = L.wrnn_taco_decode_forced(device, ctypes.byref(self.decoder_weights()), ctypes.byref(call[0]))
+            if rc != _lib.WRNN_OK:
+                raise _lib.WrnnError(f'wrnn_taco_decode_forced failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+            self.last_decode_groups.append((len(g[0]),))
+            out.append(finish(call))
+        return out
 
     @staticmethod
     def _gta_groups(steps, max_batch):
@@ -673,7 +756,7 @@ class TacotronInference:
         return gta[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()
 
     @torch.no_grad()
-    def forward_gta_batch(self, list_of_ids, list_of_mels, kernel=True, cbhg_kernel=False, max_batch=8):
+    def forward_gta_batch(self, list_of_ids, list_of_mels, kernel=True, cbhg_kernel=False, max_batch=8, groups=1):
         """`forward_gta()` for a list of utterances: a list of (gta, linear, attention), one per utterance in the caller's order, as
         `forward_gta()` returns them (see there for the two deliberate differences from the reference's script: eval mode, and every sentence
         decoded as if alone -- the result does not depend on what rides along).
@@ -683,7 +766,10 @@ class TacotronInference:
         `_lib.TACO_BATCH_NMAX` (256) ids goes through the EAGER loop on the device: there is no single-sentence forced kernel.
         cbhg_kernel=True: `encode_kernel_many` / `postnet_kernel_many` over all sentences (64 per call) and ONE transfer at the end, exactly as
         `generate_batch` does; otherwise the encoder and the post-net run per sentence on the torch ops.  kernel=False: a loop of
-        `forward_gta(kernel=False)`, on any device."""
+        `forward_gta(kernel=False)`, on any device.
+
+        groups=2 (opt-in; a device of 256 CUs): consecutive groups of the sorted order ride in pairs on ONE `wrnn_taco_decode_forced_groups`
+        launch, as in `generate_batch`; `last_decode_groups` lists what ran."""
         from . import _lib
         if len(list_of_ids) != len(list_of_mels):
             raise ValueError(f'{len(list_of_ids)} id lists for {len(list_of_mels)} mels')
@@ -691,6 +777,7 @@ class TacotronInference:
             return [self.forward_gta(ids, mel, kernel=False, cbhg_kernel=cbhg_kernel) for ids, mel in zip(list_of_ids, list_of_mels)]
         if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
             raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
+        self._pair_groups([], groups)                                              # (ValueError for anything but 1 or 2)
         dev = self.device
         if cbhg_kernel and dev.type != 'cuda':
             raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
@@ -708,10 +795,15 @@ class TacotronInference:
         decoded = [None] * len(encs)
         short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
         steps = [(ms[i].size(1) + self.r - 1) // self.r for i in short]
-        for group in self._gta_groups(steps, int(max_batch)):
-            idx = [short[j] for j in group]
-            for i, d in zip(idx, self._decode_forced_kernel([encs[i] for i in idx], [ms[i] for i in idx])):
-                decoded[i] = d
+        self.last_decode_groups = []
+        for launch in self._pair_groups([[short[j] for j in group] for group in self._gta_groups(steps, int(max_batch))], groups):
+            if len(launch) == 1:
+                results = [self._decode_forced_kernel([encs[i] for i in launch[0]], [ms[i] for i in launch[0]])]
+            else:                                                                  # neighbours in the order of step counts: they end together
+                results = self._decode_forced_launch([([encs[i] for i in idx], [ms[i] for i in idx]) for idx in launch])
+            for idx, result in zip(launch, results):
+                for i, d in zip(idx, result):
+                    decoded[i] = d
         for i, e in enumerate(encs):
             if decoded[i] is None:                                                 # more than 256 ids: the eager loop on the device
                 decoded[i] = self._decode_forced_eager(e[0], e[1], ms[i])
