@@ -74,6 +74,17 @@ enum {
                                16 * 4 * (up4(1 + feat + aux) + 2 * up4(max(rnn, fc) + aux) + 2 * up4(rnn)) + 2560 bytes (up4: rounded up to a multiple of 4),
                                and must fit one CU's 160 KiB = 163840 (rnn = fc = 512, feat 80, aux 32: 145152; rnn = fc = 576 still fits, 640 does not); RAW: <= 2048
                                classes.  Other dims: WRNN_ERR_ARG with the bytes needed -- stay on `auto` */
+    WRNN_ALGO_TILE_SPARSE = 12, /* WRNN_ALGO_TILE for a PRUNED model of non-shipped dims (csrc/wrnn_tile_sparse.hip, wrnn_tile_sparse_kernel; on request only): the
+                               same dataflow, LDS rule, workspace and options, but the four GRU matrices -- and fc1 / fc2 -- run as gathered block-sparse MFMA
+                               stages over the pack's TILE-SPARSE VIEW, so the pruned 16x1 blocks are neither streamed nor multiplied.  wrnn_pack_create builds
+                               the view for a generic pack (wrnn_pack_tile_sparse()): a block row is 16 consecutive rows of one gate (GRU: 3 gates, Linear: 1), a
+                               block (block row, column -- over the whole K, aux columns included) survives if any of its 16 values is non-zero; the GRU view
+                               exists when rnn % 16 == 0 and AT MOST 41 % of the blocks of each of rnn1 / rnn2 weight_ih / weight_hh survive, the fc view in
+                               addition when fc % 16 == 0 and the same holds for fc1 and fc2.  (41 %: a model block-pruned to 60 % sparsity -- 40.01 % survive the
+                               per-gate rounding -- is the least sparse one at which the kernel measured no slower than WRNN_ALGO_TILE, profiles/tile_sparse_ab.json;
+                               at one half it ran at 0.87 x.)  Without a view: WRNN_ERR_ARG naming the matrix and its surviving
+                               fraction, or the dim -- WRNN_ALGO_TILE runs such a pack dense.  An output element is one accumulator chain over its block row's
+                               surviving columns in ascending order */
     WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
                                four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
                                (wrnn_pack_sparse_blocks) and >= 256 CUs; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
@@ -245,6 +256,20 @@ int wrnn_pack_sparse_blocks(const wrnn_pack *p);
  * too -- the reference's pruning recipe prunes them with the GRUs, notebooks/"Pruning - Scratchpad.ipynb":199-204 -- and
  * wrnn_sparse_kernel runs its GATHERED fc stages (no dense fc1 / fc2 MFMA blocks on the chain); negated: dense fc stages */
 int wrnn_pack_sparse_fc_blocks(const wrnn_pack *p);
+/* The tile-sparse view of a generic pack (WRNN_ALGO_TILE_SPARSE): 0 none (and every pack of the shipped dims), 1 the four GRU matrices, 2 fc1 / fc2 too.
+ * kept / total (either may be NULL): surviving and all 16x1 blocks of rnn1.weight_ih, rnn1.weight_hh, rnn2.weight_ih, rnn2.weight_hh, fc1.weight, fc2.weight
+ * (0 / 0 where the matrix's rows per gate are no multiple of 16: nothing was counted). */
+int wrnn_pack_tile_sparse(const wrnn_pack *p, int32_t kept[6], int32_t total[6]);
+/* Test hook, host only (no device, the HIP runtime is not touched): the packing routine of the tile-sparse view on ONE row-major matrix W [rows][K] of
+ * `gates` gates (rows / gates a multiple of 16).  Returns the number of 16-column GROUPS of the packed lists (or WRNN_ERR_ARG) and fills
+ *   tab   [rows / 16][2]        per block row: the first group of its list | its surviving columns n (ascending; groups: (n + 15) / 16)
+ *   kept, total, admitted       surviving / all blocks; 1 when wrnn_pack_create admits this matrix to a view (at most 41 % survive: 100 * kept <= 41 * total), else 0
+ * and, when cols and vals are non-NULL and the groups fit group_capacity,
+ *   cols  [groups][4 kq][4 e]   the column of list entry 16 g + 4 e + kq of the block row that owns group g
+ *   vals  [groups][64 l][4 e]   W[16 block row + (l & 15)][column of list entry 16 g + 4 e + (l >> 4)]
+ * entries past n: value 0.0f, column = the last surviving one (a padded term is an exact no-op on finite activations); an empty list has no group. */
+int wrnn_debug_tile_sparse_pack(const float *W, int32_t rows, int32_t K, int32_t gates, int32_t *tab, int32_t *cols, float *vals,
+                                int32_t group_capacity, int32_t *kept, int32_t *total, int32_t *admitted);
 
 /* Workspace (device bytes) wrnn_generate needs for this geometry under these options (NULL = defaults).  With the loop
  * kernel it does not grow with T: conditioning is produced in slabs (942 segments x 12,100 steps: < 1 GB). */
@@ -356,7 +381,10 @@ typedef struct wrnn_plan_traits {
     int32_t mode, C;           /* WRNN_MODE_*, n_classes */
     int32_t generic;           /* non-shipped dims (wrnn_generic_kernel only) ... */
     int32_t gH, gF, gM, gA;    /* ... rnn, fc, feat, aux dims of such a pack (they appear in a message only) */
-    int32_t sp_nbp;            /* 0: the GRU matrices are not block-sparse enough for wrnn_sparse_kernel; else the padded blocks per block row, 48 / 64 */
+    int32_t sp_nbp;            /* 0: the GRU matrices are not block-sparse enough for wrnn_sparse_kernel; else the padded blocks per block row, 48 / 64.
+                                  A GENERIC pack (wrnn_sparse_kernel never runs it): > 0: it has a tile-sparse view (WRNN_ALGO_TILE_SPARSE), sp_fc = 1: with fc1 / fc2;
+                                  < 0: none, -(1 + 1001 m + f) names the first GRU matrix m (0 rnn1 ih, 1 rnn1 hh, 2 rnn2 ih, 3 rnn2 hh) that keeps more than
+                                  41 % of its blocks and its surviving fraction f in 1/1000 (a message only); 0: none (gH % 16, or nothing recorded) */
     int32_t sp_max_blocks;     /* |wrnn_pack_sparse_blocks()| (a message only) */
     int32_t sp_fc;             /* 1: fc1 / fc2 are block-sparse too (wrnn_pack_sparse_fc_blocks() > 0).  Recorded; no planning decision reads it */
 } wrnn_plan_traits;

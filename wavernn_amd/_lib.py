@@ -17,12 +17,13 @@ ERR_NO_DEVICE = -2          # WRNN_ERR_NO_DEVICE
 ERR_RESIDENCY = -6          # WRNN_ERR_RESIDENCY: the persistent grid cannot be co-resident on this device
 MODE_RAW, MODE_MOL = 0, 1
 ABI_VERSION = 9
-ALGO_AUTO, ALGO_STREAM, ALGO_LOOP, ALGO_SPARSE, ALGO_DUO, ALGO_CHAIN, ALGO_OCTO, ALGO_TILE = 0, 1, 2, 5, 6, 7, 8, 10
-ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': ALGO_SPARSE, 'duo': ALGO_DUO, 'chain': ALGO_CHAIN, 'octo': ALGO_OCTO, 'tile': ALGO_TILE}
+ALGO_AUTO, ALGO_STREAM, ALGO_LOOP, ALGO_SPARSE, ALGO_DUO, ALGO_CHAIN, ALGO_OCTO, ALGO_TILE, ALGO_TILE_SPARSE = 0, 1, 2, 5, 6, 7, 8, 10, 12
+ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': ALGO_SPARSE, 'duo': ALGO_DUO, 'chain': ALGO_CHAIN, 'octo': ALGO_OCTO, 'tile': ALGO_TILE,
+         'tile_sparse': ALGO_TILE_SPARSE}
 
 #: every symbol include/wavernn_amd.h declares
 EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_create', 'wrnn_pack_destroy',
-           'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
+           'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_pack_tile_sparse', 'wrnn_debug_tile_sparse_pack', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
            'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_nll', 'wrnn_nll_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_workspace_bytes_many',
@@ -229,6 +230,10 @@ def lib():
     L.wrnn_pack_weight_bytes.restype = ctypes.c_size_t
     L.wrnn_pack_sparse_blocks.argtypes = [ctypes.c_void_p]
     L.wrnn_pack_sparse_fc_blocks.argtypes = [ctypes.c_void_p]
+    L.wrnn_pack_tile_sparse.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32 * 6), ctypes.POINTER(ctypes.c_int32 * 6)]
+    L.wrnn_debug_tile_sparse_pack.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(ctypes.c_int32)]
     L.wrnn_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(Geometry), ctypes.POINTER(Options)]
     L.wrnn_workspace_bytes.restype = ctypes.c_size_t
     L.wrnn_generate.argtypes = [ctypes.c_void_p, ctypes.POINTER(Geometry), ctypes.c_void_p, ctypes.c_void_p,
@@ -351,3 +356,20 @@ def noise_fill_host(mode, n_segments, n_classes, t_begin, t_end, seed, seg_id=No
     check(lib().wrnn_noise_fill_host(MODE_MOL if mol else MODE_RAW, n_segments, n_classes, t_begin, t_end, int(seed) & (2 ** 64 - 1),
                                      None if ids is None else ids.ctypes.data, out.ctypes.data), 'wrnn_noise_fill_host')
     return out
+
+
+def tile_sparse_pack_host(W, gates):
+    """`wrnn_debug_tile_sparse_pack`: the tile-sparse view (WRNN_ALGO_TILE_SPARSE) of one float32 matrix W (rows, K) of `gates` gates, as the library packs it.
+    Returns dict(tab (rows / 16, 2), cols (groups, 4, 4) [kq][e], vals (groups, 64, 4) [lane][e], kept, total, admitted).  No HIP device is needed."""
+    import numpy as np
+    W = np.ascontiguousarray(W, np.float32)
+    rows, K = W.shape
+    tab = np.zeros((max(rows // 16, 1), 2), np.int32)
+    kept, total, adm = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    groups = lib().wrnn_debug_tile_sparse_pack(W.ctypes.data, rows, K, gates, tab.ctypes.data, None, None, 0, ctypes.byref(kept), ctypes.byref(total), ctypes.byref(adm))
+    if groups < 0:
+        check(groups, 'wrnn_debug_tile_sparse_pack')
+    cols, vals = np.full((groups, 4, 4), -1, np.int32), np.full((groups, 64, 4), np.nan, np.float32)
+    check(min(0, lib().wrnn_debug_tile_sparse_pack(W.ctypes.data, rows, K, gates, tab.ctypes.data, cols.ctypes.data, vals.ctypes.data, groups,
+                                                   ctypes.byref(kept), ctypes.byref(total), ctypes.byref(adm))), 'wrnn_debug_tile_sparse_pack')
+    return dict(tab=tab, cols=cols, vals=vals, kept=int(kept.value), total=int(total.value), admitted=bool(adm.value))

@@ -32,6 +32,7 @@ bool generic_dims_ok(int H, int F, int M, int A, int C, int mode);
 hipError_t launch_tile(const GenArgs &args, int mode, hipStream_t stream);
 size_t tile_lds_bytes(int H, int F, int M, int A, int C);
 bool tile_dims_ok(int H, int F, int M, int A, int C, int mode);
+hipError_t launch_tile_sparse(const GenArgs &args, const TileSparseArgs &sp, int mode, bool fcs, hipStream_t stream);
 hipError_t launch_duo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int duo_max_depth();
 size_t duo_xbuf_bytes(int G);
@@ -89,6 +90,11 @@ struct wrnn_pack {
     const float *u1;           // MOL: rnn1.weight_ih . I.weight[:,0] [3H] -- the x_{t-1} term of rnn1's gi (wrnn_duo.hip)
     // dimension-generic pack (any hparams but the shipped ones): only the k-major copies + biases, run by wrnn_generic_kernel
     const float *g_I_T, *g_fc1T, *g_fc2T, *g_w_ih2T;      // (the other k-major copies are the fields above)
+    // ... and its tile-sparse view (wrnn_tile_sparse.hip): 0 none, 1 the four GRU matrices, 2 fc1 / fc2 too; surviving / all 16x1 blocks of w_ih1, w_hh1, w_ih2,
+    // w_hh2, fc1, fc2 (0 / 0: the matrix's row count is no multiple of 16, nothing was counted)
+    int ts_view;
+    int32_t ts_kept[6], ts_total[6];
+    TileSparseArgs ts;
     const float *sp_vals;
     const int *sp_cols;
     int sp_fc_max_blocks;      // fc1 / fc2 (columns [0, H): the aux columns live in the per-frame tables): largest block row
@@ -131,7 +137,64 @@ struct Builder {
         return off;
     }
 };
+
+// The tile-sparse view of one matrix W [rows][K] (row-major, rows a multiple of 16): the layout of TileSparseMat (wrnn_device.h).  Host only.
+struct TileSparsePacked {
+    std::vector<int32_t> tab, cols;     // [rows / 16][2], [groups][16]
+    std::vector<float> vals;            // [groups][64][4]
+    int kept, total;                    // surviving / all 16x1 blocks
+};
+void tile_sparse_pack(const float *W, int rows, int K, TileSparsePacked &o)
+{
+    const int nbr = rows / 16;
+    o.tab.assign((size_t)2 * nbr, 0); o.cols.clear(); o.vals.clear();
+    o.kept = 0; o.total = nbr * K;
+    std::vector<int> cv;
+    for (int br = 0; br < nbr; ++br) {
+        const float *base = W + (size_t)16 * br * K;
+        cv.clear();
+        for (int c = 0; c < K; ++c) {
+            bool nz = false;
+            for (int r = 0; r < 16 && !nz; ++r) nz = base[(size_t)r * K + c] != 0.0f;
+            if (nz) cv.push_back(c);
+        }
+        const int n = (int)cv.size(), ng = (n + 15) / 16, g0 = (int)(o.cols.size() / 16);
+        o.kept += n;
+        o.tab[2 * br] = g0; o.tab[2 * br + 1] = n;
+        o.cols.resize((size_t)(g0 + ng) * 16);
+        o.vals.resize((size_t)(g0 + ng) * 256);
+        for (int g = 0; g < ng; ++g)
+            for (int kq = 0; kq < 4; ++kq)
+                for (int e = 0; e < 4; ++e) {
+                    const int k = 16 * g + 4 * e + kq;                  // list entry; past the list: padding = value 0 at the last surviving column
+                    const int c = k < n ? cv[k] : cv[n - 1];
+                    o.cols[((size_t)(g0 + g) * 4 + kq) * 4 + e] = c;
+                    for (int i = 0; i < 16; ++i) o.vals[(((size_t)(g0 + g) * 64) + 16 * kq + i) * 4 + e] = k < n ? base[(size_t)i * K + c] : 0.0f;
+                }
+    }
+}
+// a view needs at most 41 % of a matrix's blocks to survive (include/wavernn_amd.h, WRNN_ALGO_TILE_SPARSE): the 60 % sparsity level of `prune.block_mask`, whose
+// per-gate rounding keeps 40.01 %, is the least sparse one at which wrnn_tile_sparse_kernel measured no slower than wrnn_tile_kernel (profiles/tile_sparse_ab.json:
+// 91.8 vs 92.6 us per step; at 50 % it is 0.87 x)
+bool tile_sparse_admits(int kept, int total) { return total > 0 && 100 * (long)kept <= 41 * (long)total; }
 }  // namespace
+
+extern "C" int wrnn_debug_tile_sparse_pack(const float *W, int32_t rows, int32_t K, int32_t gates, int32_t *tab, int32_t *cols, float *vals,
+                                           int32_t group_capacity, int32_t *kept, int32_t *total, int32_t *admitted)
+{
+    if (!W || !tab || !kept || !total || !admitted || rows < 1 || K < 1 || gates < 1 || rows % gates) { set_err("bad argument"); return WRNN_ERR_ARG; }
+    if ((rows / gates) % 16) { set_err("%d rows per gate: no multiple of 16", rows / gates); return WRNN_ERR_ARG; }
+    TileSparsePacked pk;
+    tile_sparse_pack(W, rows, K, pk);
+    const int groups = (int)(pk.cols.size() / 16);
+    memcpy(tab, pk.tab.data(), pk.tab.size() * sizeof(int32_t));
+    *kept = pk.kept; *total = pk.total; *admitted = tile_sparse_admits(pk.kept, pk.total) ? 1 : 0;
+    if (cols && vals && groups <= group_capacity) {
+        memcpy(cols, pk.cols.data(), pk.cols.size() * sizeof(int32_t));
+        memcpy(vals, pk.vals.data(), pk.vals.size() * sizeof(float));
+    }
+    return groups;
+}
 
 extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **out)
 {
@@ -170,6 +233,26 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         const size_t of1 = b.add_T(w->fc1_w, gF, gH + gA, 0, gH + gA), of1b = b.add(w->fc1_b, gF);
         const size_t of2 = b.add_T(w->fc2_w, gF, gF + gA, 0, gF + gA), of2b = b.add(w->fc2_b, gF);
         const size_t of3 = b.add_T(w->fc3_w, C, gF, 0, gF), of3b = b.add(w->fc3_b, C);
+        // ---- the tile-sparse view (wrnn_tile_sparse.hip): the GRU matrices when rnn % 16 == 0 and at most 41 % of the blocks of each survive (tile_sparse_admits); fc1 / fc2 in
+        // addition when fc % 16 == 0 and the same holds for both.  The dense copies above stay: `tile` and `auto` run the pack as before
+        const float *ts_src[6] = {w->w_ih1, w->w_hh1, w->w_ih2, w->w_hh2, w->fc1_w, w->fc2_w};
+        const int ts_rows[6] = {3 * gH, 3 * gH, 3 * gH, 3 * gH, gF, gF}, ts_K[6] = {gH, gH, gH + gA, gH, gH + gA, gF + gA};
+        TileSparsePacked ts_pk[6];
+        int32_t ts_kept[6] = {0}, ts_total[6] = {0};
+        size_t ts_off[6][3] = {{0}};
+        bool gru_ok = gH % 16 == 0, fc_ok = gF % 16 == 0;
+        for (int m = 0; m < 6; ++m) {
+            if (m < 4 ? gH % 16 : gF % 16) continue;
+            tile_sparse_pack(ts_src[m], ts_rows[m], ts_K[m], ts_pk[m]);
+            ts_kept[m] = ts_pk[m].kept; ts_total[m] = ts_pk[m].total;
+            if (!tile_sparse_admits(ts_kept[m], ts_total[m])) (m < 4 ? gru_ok : fc_ok) = false;
+        }
+        const int ts_view = !gru_ok ? 0 : fc_ok ? 2 : 1;
+        for (int m = 0; m < (ts_view == 2 ? 6 : ts_view == 1 ? 4 : 0); ++m) {      // (ints stored in the float builder: same width)
+            ts_off[m][0] = b.add(ts_pk[m].vals.data(), ts_pk[m].vals.size());
+            ts_off[m][1] = b.add(reinterpret_cast<const float *>(ts_pk[m].cols.data()), ts_pk[m].cols.size());
+            ts_off[m][2] = b.add(reinterpret_cast<const float *>(ts_pk[m].tab.data()), ts_pk[m].tab.size());
+        }
         b.add(nullptr, 64);
         wrnn_pack *p = new wrnn_pack();
         memset(p, 0, sizeof *p);
@@ -189,6 +272,20 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         p->g_fc1T = base + of1; p->fc1_b = base + of1b; p->g_fc2T = base + of2; p->fc2_b = base + of2b;
         p->fc3T = base + of3; p->fc3_b = base + of3b;
         p->tr.sp_max_blocks = gH;
+        p->ts_view = ts_view;
+        for (int m = 0; m < 6; ++m) {
+            p->ts_kept[m] = ts_kept[m]; p->ts_total[m] = ts_total[m];
+            if (m < (ts_view == 2 ? 6 : ts_view == 1 ? 4 : 0))
+                p->ts.m[m] = TileSparseMat{base + ts_off[m][0], reinterpret_cast<const int *>(base + ts_off[m][1]), reinterpret_cast<const int *>(base + ts_off[m][2])};
+        }
+        // what the planner reads of it (wrnn_plan_traits of a GENERIC pack): sp_nbp > 0 a view, sp_fc its fc half; sp_nbp < 0 names the first matrix that
+        // keeps too many of its blocks, -(1 + 1001 m + its surviving fraction in 1/1000, rounded up)
+        p->tr.sp_nbp = ts_view ? 1 : 0; p->tr.sp_fc = ts_view == 2 ? 1 : 0;
+        for (int m = 0; m < 4 && !ts_view && gH % 16 == 0; ++m)
+            if (!tile_sparse_admits(ts_kept[m], ts_total[m])) {
+                p->tr.sp_nbp = -(1 + 1001 * m + (int)(((long)ts_kept[m] * 1000 + ts_total[m] - 1) / ts_total[m]));
+                break;
+            }
         p->tr.struct_bytes = (int32_t)sizeof p->tr;
         *out = p;
         return WRNN_OK;
@@ -352,8 +449,19 @@ extern "C" void wrnn_pack_destroy(wrnn_pack *p)
 
 extern "C" size_t wrnn_pack_weight_bytes(const wrnn_pack *p) { return p ? p->weight_bytes : 0; }
 
-extern "C" int wrnn_pack_sparse_blocks(const wrnn_pack *p) { return p ? (p->tr.sp_nbp ? p->tr.sp_max_blocks : -p->tr.sp_max_blocks) : 0; }
+// (a generic pack never runs on wrnn_sparse_kernel; its sp_nbp speaks of the tile-sparse view)
+extern "C" int wrnn_pack_sparse_blocks(const wrnn_pack *p) { return p ? (p->tr.sp_nbp && !p->tr.generic ? p->tr.sp_max_blocks : -p->tr.sp_max_blocks) : 0; }
 extern "C" int wrnn_pack_sparse_fc_blocks(const wrnn_pack *p) { return p ? (p->sp_fc_vals ? p->sp_fc_max_blocks : -p->sp_fc_max_blocks) : 0; }
+
+extern "C" int wrnn_pack_tile_sparse(const wrnn_pack *p, int32_t kept[6], int32_t total[6])
+{
+    if (!p) return 0;
+    for (int m = 0; m < 6; ++m) {
+        if (kept) kept[m] = p->tr.generic ? p->ts_kept[m] : 0;
+        if (total) total[m] = p->tr.generic ? p->ts_total[m] : 0;
+    }
+    return p->tr.generic ? p->ts_view : 0;
+}
 
 struct wrnn_timer {
     int device;
@@ -434,7 +542,7 @@ int enqueue_progress(const wrnn_options *o, int done, int T, int n, hipStream_t 
     return WRNN_OK;
 }
 
-enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, N_KINDS };
+enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, K_TILE_SPARSE, N_KINDS };
 constexpr int DUO_TAB_FPS = 8;       // rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
 constexpr bool DUO_AUTO = true;      // `auto` runs MoL on wrnn_duo_kernel at every depth (round 4, profiles/r04a_probe_new.json: 13.5 vs 16.6 us per step
                                      // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
@@ -481,6 +589,8 @@ const KindDesc KINDS[N_KINDS] = {
                      [](const LoopArgs &a, int, int nbp, int mode, hipStream_t s) { return launch_sparse(a, nbp, mode, s); }},
     // (wrnn_generic_kernel's dataflow and pack, one workgroup per 16 segments; on request)
     /* K_TILE    */ {"wrnn_tile_kernel", 16, 0, false, false, false},
+    // (wrnn_tile_kernel with the GRU -- and fc1 / fc2 -- stages on the pack's tile-sparse view; on request)
+    /* K_TILE_SPARSE */ {"wrnn_tile_sparse_kernel", 16, 0, false, false, false},
 };
 
 // what a call will run: kernel, split, rounds, slab length
@@ -573,7 +683,7 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     const bool partial = pl->t0 != 0 || pl->t1 != T;
     const int algo = o->algo;
     if (algo != WRNN_ALGO_AUTO && algo != WRNN_ALGO_STREAM && algo != WRNN_ALGO_LOOP && algo != WRNN_ALGO_SPARSE && algo != WRNN_ALGO_DUO && algo != WRNN_ALGO_CHAIN &&
-        algo != WRNN_ALGO_OCTO && algo != WRNN_ALGO_TILE) {
+        algo != WRNN_ALGO_OCTO && algo != WRNN_ALGO_TILE && algo != WRNN_ALGO_TILE_SPARSE) {
         set_err("unknown algo %d", algo);
         return WRNN_ERR_ARG;
     }
@@ -602,6 +712,33 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
         if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
         if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_kernel)"); return WRNN_ERR_ARG; }
         pl->kind = K_TILE;
+        return WRNN_OK;
+    }
+    if (algo == WRNN_ALGO_TILE_SPARSE) {        // on request only: wrnn_tile_kernel on the pack's tile-sparse view (csrc/wrnn_tile_sparse.hip)
+        if (!p->generic) {
+            set_err("wrnn_tile_sparse_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo "
+                    "auto picks its kernel, wrnn_sparse_kernel for a block-sparse one", H);
+            return WRNN_ERR_ARG;
+        }
+        if (p->sp_nbp <= 0) {
+            static const char *const names[4] = {"rnn1.weight_ih", "rnn1.weight_hh", "rnn2.weight_ih", "rnn2.weight_hh"};
+            const int v = -p->sp_nbp - 1;
+            if (p->gH % 16) set_err("wrnn_tile_sparse_kernel: this pack has no tile-sparse view -- rnn %d is no multiple of 16 (a block row is 16 rows of one gate); "
+                                    "algo tile runs it dense", p->gH);
+            else if (p->sp_nbp < 0 && v / 1001 < 4)
+                set_err("wrnn_tile_sparse_kernel: this pack has no tile-sparse view -- %.1f %% of the 16x1 blocks of %s survive, a view needs at most 41 %% in each of "
+                        "the four GRU matrices; algo tile runs it dense", 0.1 * (v % 1001), names[v / 1001]);
+            else set_err("wrnn_tile_sparse_kernel: this pack has no tile-sparse view (wrnn_pack_tile_sparse() == 0); algo tile runs it dense");
+            return WRNN_ERR_ARG;
+        }
+        if (!tile_dims_ok(p->gH, p->gF, p->gM, p->gA, p->C, p->mode)) {
+            set_err("wrnn_tile_sparse_kernel: rnn %d, fc %d, feat %d, aux %d, %d classes need %zu bytes of LDS per workgroup, the limit is %d (and RAW: <= 2048 classes); "
+                    "algo auto runs this pack on wrnn_generic_kernel", p->gH, p->gF, p->gM, p->gA, p->C, tile_lds_bytes(p->gH, p->gF, p->gM, p->gA, p->C), 160 * 1024);
+            return WRNN_ERR_ARG;
+        }
+        if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
+        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_sparse_kernel)"); return WRNN_ERR_ARG; }
+        pl->kind = K_TILE_SPARSE;
         return WRNN_OK;
     }
     if (p->generic) {           // non-shipped hparams: the dimension-generic kernel is the only one that takes them without being asked for by name
@@ -710,7 +847,7 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
     l.xcc = o;    o = al(o + XCC_WORDS * sizeof(unsigned));
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE) {
         l.nlib = o; if (noise_lib) o = al(o + (size_t)T * noise_row);
         l.total = o;
         return l;
@@ -884,7 +1021,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         HIPCHK(hipMemcpyAsync(ws + l.segs + (size_t)2 * B * sizeof(int), o->seg_moff, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
         HIPCHK(launch_put_floats((float *)(ws + l.melc), coef, 3 * LAST_SCALE, stream));       // (by value, as kernel arguments: `coef` is a stack array)
     }
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE) {
         GenArgs g;
         memset(&g, 0, sizeof g);
         g.I_T = p->g_I_T; g.I_b = p->I_b; g.w_ih1T = p->w_ih1T; g.w_hh1T = p->w_hh1T; g.b_ih1 = p->b_ih1; g.b_hh1 = p->b_hh1;
@@ -898,7 +1035,10 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         }
         g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
-        HIPCHK(pl.kind == K_TILE ? launch_tile(g, p->tr.mode, stream) : launch_generic(g, p->tr.mode, stream));
+        if (pl.kind == K_TILE_SPARSE && !p->ts_view) { set_err("this pack has no tile-sparse view"); return WRNN_ERR_ARG; }      // (the planner's traits are the pack's own: never)
+        HIPCHK(pl.kind == K_TILE_SPARSE ? launch_tile_sparse(g, p->ts, p->tr.mode, p->ts_view == 2, stream)
+               : pl.kind == K_TILE      ? launch_tile(g, p->tr.mode, stream)
+                                        : launch_generic(g, p->tr.mode, stream));
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         wrnn_run_info gi;
         memset(&gi, 0, sizeof gi);

@@ -149,6 +149,20 @@ struct GenArgs {
     int H, F, M, A, C, B, T, hop;
 };
 
+// The tile-sparse view of one matrix of a generic pack (wrnn_tile_sparse.hip; built by tile_sparse_pack of wrnn_abi.hip).  A BLOCK ROW is 16 consecutive
+// rows (of one gate: the gates' row counts are multiples of 16), its list the columns in which any of the 16 values is non-zero, ascending, padded to whole
+// GROUPS of 16 columns with value 0.0f at a valid column (the last surviving one; 0 for an empty list).
+//   tab    [block rows][2]       first group of the block row's list | surviving columns n (its groups: (n + 15) / 16, its k-steps of four columns: (n + 3) / 4)
+//   cols   [groups][4 kq][4 e]   the column of list entry 16 group + 4 e + kq: what lane l = 16 kq + i feeds k-step e of the group, one 16-byte load per lane
+//   vals   [groups][64 l][4 e]   W[16 block row + (l & 15)][that column]: the A operand A[i = l & 15][k = l >> 4] of k-step e, one 16-byte load per lane
+struct TileSparseMat {
+    const float *vals;
+    const int *cols, *tab;
+};
+struct TileSparseArgs {
+    TileSparseMat m[6];                 // w_ih1, w_hh1, w_ih2, w_hh2, fc1, fc2 (the last two: only with the fc view)
+};
+
 // arguments of the hoisted-conditioning kernels (wrnn_cond.hip)
 struct CondArgs {
     const float *mels_up;   // [L][MEL]

@@ -124,6 +124,13 @@ class LoopEngine:
         """> 0: fc1 / fc2 are block-sparse too (the notebook's recipe prunes the Linear layers) -> the sparse kernel's gathered fc stages."""
         return int(self.lib.wrnn_pack_sparse_fc_blocks(self._pack))
 
+    def tile_sparse_view(self):
+        """(view, kept, total) of `wrnn_pack_tile_sparse`: view 0 -- algo='tile_sparse' refuses this pack --, 1 (the GRU matrices run on their surviving 16x1
+        blocks) or 2 (fc1 / fc2 too); kept / total: surviving and all blocks of rnn1 ih, rnn1 hh, rnn2 ih, rnn2 hh, fc1, fc2."""
+        kept, total = (ctypes.c_int32 * 6)(), (ctypes.c_int32 * 6)()
+        view = int(self.lib.wrnn_pack_tile_sparse(self._pack, ctypes.byref(kept), ctypes.byref(total)))
+        return view, [int(k) for k in kept], [int(t) for t in total]
+
     @property
     def weight_bytes(self):
         return int(self.lib.wrnn_pack_weight_bytes(self._pack))

@@ -57,7 +57,8 @@ def main(argv=None):
                     help='a pruned MoL model on wrnn_sparse_kernel: groups of segments per cluster (2: 512 segments a round; a dense model ignores it)')
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
-                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup")
+                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
+                         "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones")
     a = ap.parse_args(argv)
     if a.noise in ('cpu', 'library') and a.seed is None:
         ap.error(f'--noise {a.noise} needs --seed')

@@ -58,7 +58,8 @@ def main(argv=None):
                          'the loop from a counter-based generator -- the utterance sounds the same alone and in any gen_corpus batch with the same seed')
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
-                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup")
+                         "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
+                         "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones")
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():

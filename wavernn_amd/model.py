@@ -137,7 +137,7 @@ class WaveRNN(nn.Module):
         self.noise_seed = 0
         #: ... and the generator's key (wrnn_options.noise_seed), shared by every call of this model
         self.noise_key = 0
-        #: 'auto' | 'loop' | 'sparse' | 'stream' | ... (`_lib.ALGOS`: WRNN_ALGO_*, include/wavernn_amd.h); 'tile': a model of other dims than the shipped ones on
+        #: 'auto' | 'loop' | 'sparse' | 'stream' | ... (`_lib.ALGOS`: WRNN_ALGO_*, include/wavernn_amd.h); 'tile' / 'tile_sparse' (pruned): a model of other dims than the shipped ones on
         #: wrnn_tile_kernel (16 segments per workgroup) instead of `auto`'s wrnn_generic_kernel (one)
         self.loop_algo = 'auto'
         #: 2 = a run planned on wrnn_sparse_kernel puts TWO groups of <= 16 segments on each of its 16 clusters (wrnn_options.sparse_groups: 512 segments a

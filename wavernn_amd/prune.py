@@ -11,6 +11,11 @@ The dense loop kernels run the pruned model as masked dense weights (parity: tes
 loop kernel (wrnn_sparse_kernel) packs the surviving 16x1 blocks and turns the 95 % zeros into speed: `auto` runs it for a
 MoL model, and for a 9-bit RAW model on request (`model.loop_algo = 'sparse'`; `auto` keeps the dense kernels for RAW,
 whose class indices are compared bit for bit: tests/test_gpu_sparse_raw.py).  8-bit RAW runs on the dense kernels only.
+
+wrnn_sparse_kernel is built for the shipped dims (rnn = fc = 512, feat 80, aux 32).  A pruned model of ANY other dims -- rnn 256, rnn 384, 10-bit RAW at
+rnn 512 -- runs its surviving blocks on wrnn_tile_sparse_kernel (`model.loop_algo = 'tile_sparse'`, `--algo tile_sparse`; on request, `auto` runs such a
+model as masked dense weights on wrnn_generic_kernel): the pack carries a tile-sparse view when rnn % 16 == 0 and at most 41 % of the 16x1 blocks of each
+GRU matrix survive (a sparsity of 0.6 or more; below that the dense kernel is faster), and runs fc1 / fc2 on theirs when `linear=True` pruned them as well (`LoopEngine.tile_sparse_view()`).
 """
 import numpy as np
 
@@ -198,11 +203,12 @@ def wavernn_pruner(model, start_prune, prune_steps, target_sparsity=0.95, prune_
     return pruner, layers
 
 
-def score_at_sparsities(model, mels, wavs, sparsities, linear=False, block=(16, 1), mu_law=None):
+def score_at_sparsities(model, mels, wavs, sparsities, linear=False, block=(16, 1), mu_law=None, algo=None):
     """The corpus score of `model` (a `wavernn_amd.WaveRNN` on a HIP device) after block-pruning it to each of `sparsities`: for every value the
     weights are pruned with `block_prune_state_dict` (`linear`: fc1 / fc2 too), loaded into a COPY of the model and scored with
     `batch.score_corpus` on the copy's `loop_algo` -- `auto` runs a qualifying MoL pack on wrnn_sparse_kernel, so the score comes from the kernel
-    that would generate the audio.  Returns [(sparsity, nll_mean over all counted steps, the loop kernel that ran)]; the caller's model keeps its
+    that would generate the audio (algo: another one for these calls, e.g. 'tile_sparse' for a model of other dims than the shipped ones, whose pruned
+    packs `auto` runs dense).  Returns [(sparsity, nll_mean over all counted steps, the loop kernel that ran)]; the caller's model keeps its
     weights and its device packs."""
     import copy
     import torch
@@ -218,7 +224,7 @@ def score_at_sparsities(model, mels, wavs, sparsities, linear=False, block=(16, 
         finally:
             model._engine, model._pre = engines
         m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pruned.items()}, strict=False)
-        res = score_corpus(m, mels, wavs, mu_law=mu_law)
+        res = score_corpus(m, mels, wavs, mu_law=mu_law, algo=algo)
         out.append((float(z), sum(r['nll_sum'] for r in res) / sum(r['steps'] for r in res), m.last_loop_kernel))
         del m
     return out
