@@ -4,7 +4,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/wavernn_amd.h"
 #include "wrnn_device.h"
+
+// host side (wrnn_taco.hip): the message behind wrnn_taco_last_error(), and the one check of the geometry every decoder kernel is built for
+// (T_NM .. T_AK below): WRNN_OK, or WRNN_ERR_ARG with the message behind `pre` ("" or "group g: ")
+void taco_err(const char *fmt, ...);
+int taco_check_geometry(const wrnn_taco_weights *w, const char *pre);
 
 namespace wrnn {
 
@@ -24,6 +30,10 @@ constexpr int A_PRE_IN = 0, A_PRE1 = 128, A_PRE2 = 384, A_ATTN_H = 512 /* [2][25
               A_H1 = 6144 /* [2][512] */, A_H2 = 7168, A_C1 = 8192, A_C2 = 8704, A_END = 9216;
 // then (unsigned) [T_MAXWG] arrival words, [T_MAXWG] not-below-threshold counts, [8] status
 constexpr int U_FLAG = 0, U_CNT = T_MAXWG, U_STATUS = 2 * T_MAXWG, U_END = 2 * T_MAXWG + 8;
+// the prefix of every decoder workspace, [A_END floats | U_END words]: the status words stay where wrnn_taco_status reads them; a kernel's
+// tagged vectors follow
+constexpr size_t TACO_PREFIX_BYTES = (size_t)A_END * 4 + (size_t)U_END * 4;
+static_assert(TACO_PREFIX_BYTES % 8 == 0, "tagged entries are 8-byte aligned");
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 

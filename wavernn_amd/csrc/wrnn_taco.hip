@@ -743,11 +743,17 @@ void taco_err(const char *fmt, ...)                 // (also the message buffer 
 
 extern "C" const char *wrnn_taco_last_error(void) { return g_taco_err; }
 
-// workspace: [A_END floats | U_END words] of the flag-barrier kernel (the status words live there for both kernels), then the
-// resident kernel's tagged vectors
-constexpr size_t TACO_V1_BYTES = (size_t)A_END * 4 + (size_t)U_END * 4;
-static_assert(TACO_V1_BYTES % 8 == 0, "tagged entries are 8-byte aligned");
-extern "C" size_t wrnn_taco_workspace_bytes(void) { return TACO_V1_BYTES + (size_t)(V_END + 24) * 8; }
+int taco_check_geometry(const wrnn_taco_weights *w, const char *pre)
+{
+    if (w->n_mels == T_NM && w->prenet1 == T_P1 && w->prenet2 == T_P2 && w->decoder_dims == T_DD && w->encoder_width == T_DD &&
+        w->lstm_dims == T_LD && w->attn_filters == T_AF && w->attn_kernel == T_AK)
+        return WRNN_OK;
+    taco_err("%sunsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)", pre);
+    return WRNN_ERR_ARG;
+}
+
+// workspace: the prefix of the flag-barrier kernel (the status words live there for both kernels), then the resident kernel's tagged vectors
+extern "C" size_t wrnn_taco_workspace_bytes(void) { return TACO_PREFIX_BYTES + (size_t)(V_END + 24) * 8; }
 
 extern "C" int wrnn_taco_decode(int device, const wrnn_taco_weights *w, const wrnn_taco_call *c)
 {
@@ -761,11 +767,7 @@ extern "C" int wrnn_taco_decode(int device, const wrnn_taco_weights *w, const wr
         taco_err("bad call: n=%d (1..%d) r=%d max_r=%d max_steps=%d or a null / short buffer", c->n, T_NMAX, c->r, c->max_r, c->max_steps);
         return WRNN_ERR_ARG;
     }
-    if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
-        w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
-        taco_err("unsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)");
-        return WRNN_ERR_ARG;
-    }
+    if (taco_check_geometry(w, "") != WRNN_OK) return WRNN_ERR_ARG;
     DeviceGuard dg(device);
     hipError_t e = dg.err;
     if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
@@ -779,7 +781,7 @@ extern "C" int wrnn_taco_decode(int device, const wrnn_taco_weights *w, const wr
     a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
     a.mel_out = c->mel_out; a.scores_out = c->scores_out; a.steps_done = c->steps_done;
     a.n = c->n; a.r = c->r; a.max_r = c->max_r; a.max_steps = c->max_steps;
-    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_V1_BYTES);
+    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
     a.nwg = prop.multiProcessorCount < T_MAXWG ? prop.multiProcessorCount : T_MAXWG;
     a.stop_threshold = c->stop_threshold;
     // the register-resident kernel needs exactly R_NWG co-resident workgroups (one LSTM unit per wave) and r <= R_MAXR frames per step

@@ -53,8 +53,6 @@
 // and the earlier pass says so in every instantiation)
 #pragma clang diagnostic ignored "-Wpass-failed"
 
-void taco_err(const char *fmt, ...);                                  // wrnn_taco.hip: the message behind wrnn_taco_last_error()
-
 namespace wrnn {
 
 constexpr int B_SMAX = WRNN_TACO_BATCH_MAX, B_NMAX = WRNN_TACO_BATCH_NMAX;
@@ -695,118 +693,30 @@ __global__ __launch_bounds__(NT) void wrnn_taco_prenet_kernel(const TacoPrenetAr
 
 }  // namespace wrnn
 
+// The code object holds the instantiations of wrnn_taco_batch_kernel in the order in which they are first named: pinned here (behind the
+// namespace, so that the pre-pass kernel stays in front of them), and the host code below can name them in any order.
+#define TACO_INSTANTIATE(FORCED, GROUPED)                                                                                         \
+    template __global__ void wrnn::wrnn_taco_batch_kernel<2, FORCED, GROUPED>(const wrnn::TacoKernArgsOf<FORCED, GROUPED>::type); \
+    template __global__ void wrnn::wrnn_taco_batch_kernel<4, FORCED, GROUPED>(const wrnn::TacoKernArgsOf<FORCED, GROUPED>::type); \
+    template __global__ void wrnn::wrnn_taco_batch_kernel<8, FORCED, GROUPED>(const wrnn::TacoKernArgsOf<FORCED, GROUPED>::type);
+TACO_INSTANTIATE(false, false)                                        // the plain calls: free-running, forced
+TACO_INSTANTIATE(true, false)
+TACO_INSTANTIATE(false, true)                                         // two groups per launch
+TACO_INSTANTIATE(true, true)
+#undef TACO_INSTANTIATE
+
 using namespace wrnn;
 
-// workspace: the single-sentence decoder's prefix ([A_END floats | U_END words]: the status words stay where wrnn_taco_status reads them), then
-// the tagged vectors of n_sent sentences
-constexpr size_t TACO_PREFIX_BYTES = (size_t)A_END * 4 + (size_t)U_END * 4;
-static_assert(TACO_PREFIX_BYTES % 8 == 0, "tagged entries are 8-byte aligned");
+constexpr int32_t FORCED_MAX_FRAMES = 1 << 20;
 
+// workspace: the single-sentence decoder's prefix (wrnn_taco.h), then the tagged vectors of n_sent sentences
 extern "C" size_t wrnn_taco_batch_workspace_bytes(int32_t n_sent)
 {
     if (n_sent < 1 || n_sent > B_SMAX) return 0;
     return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8;
 }
 
-// The argument checks of a free-running call: everything is checked before the first HIP call.  `pre` is "" (wrnn_taco_decode_batch) or
-// "group g: " (wrnn_taco_decode_batch_groups) in front of the message.
-static int check_batch_call(const wrnn_taco_weights *w, const wrnn_taco_batch_call *c, const char *pre)
-{
-    if (!w || !c) { taco_err("%snull argument", pre); return WRNN_ERR_ARG; }
-    if (c->struct_bytes != sizeof(wrnn_taco_batch_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
-        taco_err("%sstruct size mismatch (header / library versions differ)", pre);
-        return WRNN_ERR_ARG;
-    }
-    if (c->n_sent < 1 || c->n_sent > B_SMAX) {
-        taco_err("%sn_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", pre, c->n_sent, B_SMAX);
-        return WRNN_ERR_ARG;
-    }
-    if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
-        taco_err("%sr=%d max_r=%d: frames per step must be 1..min(max_r, %d)", pre, c->r, c->max_r, R_MAXR);
-        return WRNN_ERR_ARG;
-    }
-    if (!c->n || !c->max_steps || !c->seq || !c->seq_proj || !c->mel_out || !c->scores_out || !c->steps_done || !c->workspace) {
-        taco_err("%snull buffer: n, max_steps, seq, seq_proj, mel_out, scores_out, steps_done and workspace are all required", pre);
-        return WRNN_ERR_ARG;
-    }
-    for (int s = 0; s < c->n_sent; ++s) {
-        if (c->n[s] < 1 || c->n[s] > B_NMAX) {
-            taco_err("%ssentence %d: n=%d encoder positions, the batched kernel takes 1..%d (WRNN_TACO_BATCH_NMAX; longer: wrnn_taco_decode)", pre, s,
-                     c->n[s], B_NMAX);
-            return WRNN_ERR_ARG;
-        }
-        if (c->max_steps[s] < 1) {
-            taco_err("%ssentence %d: max_steps=%d, at least 1", pre, s, c->max_steps[s]);
-            return WRNN_ERR_ARG;
-        }
-        if (!c->seq[s] || !c->seq_proj[s] || !c->mel_out[s] || !c->scores_out[s]) {
-            taco_err("%ssentence %d: null buffer (seq, seq_proj, mel_out and scores_out are required)", pre, s);
-            return WRNN_ERR_ARG;
-        }
-    }
-    if (c->workspace_bytes < wrnn_taco_batch_workspace_bytes(c->n_sent)) {
-        taco_err("%sworkspace of %zu bytes, %d sentences need %zu (wrnn_taco_batch_workspace_bytes)", pre, c->workspace_bytes, c->n_sent,
-                 wrnn_taco_batch_workspace_bytes(c->n_sent));
-        return WRNN_ERR_ARG;
-    }
-    if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
-        w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
-        taco_err("%sunsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)", pre);
-        return WRNN_ERR_ARG;
-    }
-    return WRNN_OK;
-}
-
-// the kernel's argument block of a checked call
-static void fill_batch_args(TacoBatchArgs &a, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
-{
-    memset(&a, 0, sizeof a);
-    a.w = *w;
-    for (int s = 0; s < c->n_sent; ++s) {
-        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
-        a.s[s].n = c->n[s]; a.s[s].max_steps = c->max_steps[s];
-    }
-    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
-    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
-    a.steps_done = c->steps_done;
-    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
-    a.stop_threshold = c->stop_threshold;
-}
-
-extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c)
-{
-    // ---- arguments: everything is checked before the first HIP call ----
-    const int bad = check_batch_call(w, c, "");
-    if (bad != WRNN_OK) return bad;
-    // ---- device ----
-    DeviceGuard dg(device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    if (prop.multiProcessorCount < R_NWG) {
-        taco_err("the batched decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
-                 prop.multiProcessorCount);
-        return WRNN_ERR_RESIDENCY;
-    }
-    TacoBatchArgs a;
-    fill_batch_args(a, w, c);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
-    e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
-    if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    void *params[] = {(void *)&a};
-    const void *kern = c->n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2> : c->n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4>
-                                                                                                   : (const void *)wrnn_taco_batch_kernel<8>;
-    e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
-    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
-    return WRNN_OK;
-}
-
-// ---------------- the forced form: ground-truth-aligned mels ----------------
-constexpr int32_t FORCED_MAX_FRAMES = 1 << 20;
-
-// workspace: [the batched decoder's prefix | tagged vectors of n_sent sentences | the PreNet table, (sum of steps) rows of T_P2 floats]
+// the forced form (ground-truth-aligned mels): [the batched decoder's workspace | the PreNet table, (sum of steps) rows of T_P2 floats]
 extern "C" size_t wrnn_taco_forced_workspace_bytes(int32_t n_sent, const int32_t *frames, int32_t r)
 {
     if (n_sent < 1 || n_sent > B_SMAX || !frames || r < 1 || r > R_MAXR) return 0;
@@ -815,114 +725,143 @@ extern "C" size_t wrnn_taco_forced_workspace_bytes(int32_t n_sent, const int32_t
         if (frames[s] < 1 || frames[s] > FORCED_MAX_FRAMES) return 0;
         steps += (size_t)((frames[s] + r - 1) / r);
     }
-    return TACO_PREFIX_BYTES + (size_t)n_sent * BV_END * 8 + steps * T_P2 * 4;
+    return wrnn_taco_batch_workspace_bytes(n_sent) + steps * T_P2 * 4;
 }
 
-// The argument checks of a forced call, as check_batch_call.
-static int check_forced_call(const wrnn_taco_weights *w, const wrnn_taco_forced_call *c, const char *pre)
+// ---------------- a decoder call, free-running or forced ----------------
+// What the checks, the fill and the launch below read: the fields wrnn_taco_batch_call and wrnn_taco_forced_call share, the per-sentence step
+// source, what only one form has, and the words in which the forms' messages differ.
+struct TacoFormWords {
+    const char *kernel;                   // "the ... kernel takes", "the ... decoder kernel needs"
+    const char *longer;                   // where a sentence of more than B_NMAX positions goes
+    const char *buffers, *sent_buffers;   // what a call, and a sentence of it, must not leave null
+    const char *these, *ws_fn;            // "... sentences need N (the workspace function)"
+};
+static const TacoFormWords WORDS[2] = {
+    {"batched", "; longer: wrnn_taco_decode", "n, max_steps, seq, seq_proj, mel_out, scores_out, steps_done and workspace",
+     "seq, seq_proj, mel_out and scores_out", "", "wrnn_taco_batch_workspace_bytes"},
+    {"forced", "", "n, frames, seq, seq_proj, force_mel, mel_out, scores_out and workspace", "seq, seq_proj, force_mel, mel_out and scores_out", "these ",
+     "wrnn_taco_forced_workspace_bytes"}};
+
+struct TacoCallView {
+    const TacoFormWords *words;           // (null: the view of a null call)
+    bool forced, size_ok;                 // size_ok: struct_bytes is the size of the public struct
+    int32_t n_sent, r, max_r;
+    const int32_t *n, *count;             // count[s]: max_steps[s] (free-running) or frames[s] (forced)
+    const float *const *seq, *const *seq_proj, *const *force_mel;     // force_mel: forced only
+    float *const *mel_out, *const *scores_out;
+    int32_t *steps_done;                  // free-running only, as stop_threshold
+    float stop_threshold;
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+    int steps(int s) const { return forced ? (count[s] + r - 1) / r : count[s]; }
+};
+
+template <class Call> static TacoCallView view_shared(const Call *c, bool forced, const int32_t *count)
 {
-    if (!w || !c) { taco_err("%snull argument", pre); return WRNN_ERR_ARG; }
-    if (c->struct_bytes != sizeof(wrnn_taco_forced_call) || w->struct_bytes != sizeof(wrnn_taco_weights)) {
+    TacoCallView v = {};
+    v.words = &WORDS[forced]; v.forced = forced; v.size_ok = c->struct_bytes == sizeof(Call);
+    v.n_sent = c->n_sent; v.r = c->r; v.max_r = c->max_r;
+    v.n = c->n; v.count = count; v.seq = c->seq; v.seq_proj = c->seq_proj; v.mel_out = c->mel_out; v.scores_out = c->scores_out;
+    v.workspace = c->workspace; v.workspace_bytes = c->workspace_bytes; v.stream = c->stream;
+    return v;
+}
+static TacoCallView view_of(const wrnn_taco_batch_call *c)
+{
+    if (!c) return TacoCallView{};
+    TacoCallView v = view_shared(c, false, c->max_steps);
+    v.steps_done = c->steps_done; v.stop_threshold = c->stop_threshold;
+    return v;
+}
+static TacoCallView view_of(const wrnn_taco_forced_call *c)
+{
+    if (!c) return TacoCallView{};
+    TacoCallView v = view_shared(c, true, c->frames);
+    v.force_mel = c->force_mel;
+    return v;
+}
+
+// The argument checks of a call: everything is checked before the first HIP call.  `pre` is "" (a plain call) or "group g: " (a group of a
+// groups call) in front of the message.
+static int check_call(const wrnn_taco_weights *w, const TacoCallView &c, const char *pre)
+{
+    if (!w || !c.words) { taco_err("%snull argument", pre); return WRNN_ERR_ARG; }
+    const TacoFormWords &words = *c.words;
+    if (!c.size_ok || w->struct_bytes != sizeof(wrnn_taco_weights)) {
         taco_err("%sstruct size mismatch (header / library versions differ)", pre);
         return WRNN_ERR_ARG;
     }
-    if (c->n_sent < 1 || c->n_sent > B_SMAX) {
-        taco_err("%sn_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", pre, c->n_sent, B_SMAX);
+    if (c.n_sent < 1 || c.n_sent > B_SMAX) {
+        taco_err("%sn_sent=%d: a call decodes 1..%d sentences (WRNN_TACO_BATCH_MAX)", pre, c.n_sent, B_SMAX);
         return WRNN_ERR_ARG;
     }
-    if (c->r < 1 || c->r > c->max_r || c->r > R_MAXR) {
-        taco_err("%sr=%d max_r=%d: frames per step must be 1..min(max_r, %d)", pre, c->r, c->max_r, R_MAXR);
+    if (c.r < 1 || c.r > c.max_r || c.r > R_MAXR) {
+        taco_err("%sr=%d max_r=%d: frames per step must be 1..min(max_r, %d)", pre, c.r, c.max_r, R_MAXR);
         return WRNN_ERR_ARG;
     }
-    if (!c->n || !c->frames || !c->seq || !c->seq_proj || !c->force_mel || !c->mel_out || !c->scores_out || !c->workspace) {
-        taco_err("%snull buffer: n, frames, seq, seq_proj, force_mel, mel_out, scores_out and workspace are all required", pre);
+    if (!c.n || !c.count || !c.seq || !c.seq_proj || (c.forced && !c.force_mel) || !c.mel_out || !c.scores_out || (!c.forced && !c.steps_done) ||
+        !c.workspace) {
+        taco_err("%snull buffer: %s are all required", pre, words.buffers);
         return WRNN_ERR_ARG;
     }
-    for (int s = 0; s < c->n_sent; ++s) {
-        if (c->n[s] < 1 || c->n[s] > B_NMAX) {
-            taco_err("%ssentence %d: n=%d encoder positions, the forced kernel takes 1..%d (WRNN_TACO_BATCH_NMAX)", pre, s, c->n[s], B_NMAX);
+    for (int s = 0; s < c.n_sent; ++s) {
+        if (c.n[s] < 1 || c.n[s] > B_NMAX) {
+            taco_err("%ssentence %d: n=%d encoder positions, the %s kernel takes 1..%d (WRNN_TACO_BATCH_NMAX%s)", pre, s, c.n[s], words.kernel, B_NMAX,
+                     words.longer);
             return WRNN_ERR_ARG;
         }
-        if (c->frames[s] < 1 || c->frames[s] > FORCED_MAX_FRAMES) {
-            taco_err("%ssentence %d: frames=%d ground-truth frames, 1..%d", pre, s, c->frames[s], FORCED_MAX_FRAMES);
+        if (c.forced && (c.count[s] < 1 || c.count[s] > FORCED_MAX_FRAMES)) {
+            taco_err("%ssentence %d: frames=%d ground-truth frames, 1..%d", pre, s, c.count[s], FORCED_MAX_FRAMES);
             return WRNN_ERR_ARG;
         }
-        if (!c->seq[s] || !c->seq_proj[s] || !c->force_mel[s] || !c->mel_out[s] || !c->scores_out[s]) {
-            taco_err("%ssentence %d: null buffer (seq, seq_proj, force_mel, mel_out and scores_out are required)", pre, s);
+        if (!c.forced && c.count[s] < 1) {
+            taco_err("%ssentence %d: max_steps=%d, at least 1", pre, s, c.count[s]);
+            return WRNN_ERR_ARG;
+        }
+        if (!c.seq[s] || !c.seq_proj[s] || (c.forced && !c.force_mel[s]) || !c.mel_out[s] || !c.scores_out[s]) {
+            taco_err("%ssentence %d: null buffer (%s are required)", pre, s, words.sent_buffers);
             return WRNN_ERR_ARG;
         }
     }
-    const size_t need = wrnn_taco_forced_workspace_bytes(c->n_sent, c->frames, c->r);
-    if (c->workspace_bytes < need) {
-        taco_err("%sworkspace of %zu bytes, these %d sentences need %zu (wrnn_taco_forced_workspace_bytes)", pre, c->workspace_bytes, c->n_sent, need);
+    const size_t need = c.forced ? wrnn_taco_forced_workspace_bytes(c.n_sent, c.count, c.r) : wrnn_taco_batch_workspace_bytes(c.n_sent);
+    if (c.workspace_bytes < need) {
+        taco_err("%sworkspace of %zu bytes, %s%d sentences need %zu (%s)", pre, c.workspace_bytes, words.these, c.n_sent, need, words.ws_fn);
         return WRNN_ERR_ARG;
     }
-    if (w->n_mels != T_NM || w->prenet1 != T_P1 || w->prenet2 != T_P2 || w->decoder_dims != T_DD || w->encoder_width != T_DD ||
-        w->lstm_dims != T_LD || w->attn_filters != T_AF || w->attn_kernel != T_AK) {
-        taco_err("%sunsupported decoder geometry (the kernel is built for the reference's hparams: 80 / 256 / 128 / 256 / 512 / 32 x 31)", pre);
-        return WRNN_ERR_ARG;
-    }
-    return WRNN_OK;
+    return taco_check_geometry(w, pre);
 }
 
-// the argument blocks of a checked call: the loop's and the pre-pass's; returns the pre-pass's workgroup count
-static int fill_forced_args(TacoForcedArgs &a, TacoPrenetArgs &pa, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
+// The argument blocks of a checked call: the loop's and, FORCED, the pre-pass's.  Returns the pre-pass's workgroup count (0 free-running).
+template <bool FORCED> static int fill_args(typename TacoArgsOf<FORCED>::type &a, TacoPrenetArgs &pa, const wrnn_taco_weights *w, const TacoCallView &c)
 {
     memset(&a, 0, sizeof a);
-    memset(&pa, 0, sizeof pa);
     a.w = *w;
-    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c->workspace) + (size_t)A_END * 4);
-    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES);
-    float *pre2 = reinterpret_cast<float *>(reinterpret_cast<char *>(c->workspace) + TACO_PREFIX_BYTES + (size_t)c->n_sent * BV_END * 8);
-    a.pre2 = pre2; pa.pre2 = pre2;
-    int off = 0, wgs = 0;
-    for (int s = 0; s < c->n_sent; ++s) {
-        const int steps = (c->frames[s] + c->r - 1) / c->r;
-        a.s[s].seq = c->seq[s]; a.s[s].seq_proj = c->seq_proj[s]; a.s[s].mel_out = c->mel_out[s]; a.s[s].scores_out = c->scores_out[s];
-        a.s[s].n = c->n[s]; a.s[s].max_steps = steps;
-        a.pre_off[s] = off;
-        pa.s[s].mel = c->force_mel[s]; pa.s[s].frames = c->frames[s]; pa.s[s].steps = steps; pa.s[s].off = off; pa.s[s].wg0 = wgs;
-        off += steps;                                                  // (<= 8 * 2^20)
-        wgs += (steps + PN_CH - 1) / PN_CH;
+    a.uw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(c.workspace) + (size_t)A_END * 4);
+    a.tv = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(c.workspace) + TACO_PREFIX_BYTES);
+    for (int s = 0; s < c.n_sent; ++s) {
+        a.s[s].seq = c.seq[s]; a.s[s].seq_proj = c.seq_proj[s]; a.s[s].mel_out = c.mel_out[s]; a.s[s].scores_out = c.scores_out[s];
+        a.s[s].n = c.n[s]; a.s[s].max_steps = c.steps(s);
     }
-    a.n_sent = c->n_sent; a.r = c->r; a.max_r = c->max_r;
-    pa.fc1_w = w->prenet_fc1_w; pa.fc1_b = w->prenet_fc1_b; pa.fc2_w = w->prenet_fc2_w; pa.fc2_b = w->prenet_fc2_b;
-    pa.n_sent = c->n_sent; pa.r = c->r;
+    a.steps_done = c.steps_done;
+    a.n_sent = c.n_sent; a.r = c.r; a.max_r = c.max_r;
+    a.stop_threshold = c.stop_threshold;
+    int wgs = 0;
+    if constexpr (FORCED) {
+        memset(&pa, 0, sizeof pa);
+        a.pre2 = pa.pre2 = reinterpret_cast<float *>(reinterpret_cast<char *>(c.workspace) + wrnn_taco_batch_workspace_bytes(c.n_sent));
+        int off = 0;
+        for (int s = 0; s < c.n_sent; ++s) {
+            const int steps = c.steps(s);
+            a.pre_off[s] = off;
+            pa.s[s].mel = c.force_mel[s]; pa.s[s].frames = c.count[s]; pa.s[s].steps = steps; pa.s[s].off = off; pa.s[s].wg0 = wgs;
+            off += steps;                                                  // (<= 8 * 2^20)
+            wgs += (steps + PN_CH - 1) / PN_CH;
+        }
+        pa.fc1_w = w->prenet_fc1_w; pa.fc1_b = w->prenet_fc1_b; pa.fc2_w = w->prenet_fc2_w; pa.fc2_b = w->prenet_fc2_b;
+        pa.n_sent = c.n_sent; pa.r = c.r;
+    }
     return wgs;
-}
-
-extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c)
-{
-    // ---- arguments: everything is checked before the first HIP call ----
-    const int bad = check_forced_call(w, c, "");
-    if (bad != WRNN_OK) return bad;
-    // ---- device ----
-    DeviceGuard dg(device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    if (prop.multiProcessorCount < R_NWG) {
-        taco_err("the forced decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", R_NWG, R_NWG,
-                 prop.multiProcessorCount);
-        return WRNN_ERR_RESIDENCY;
-    }
-    TacoForcedArgs a;
-    TacoPrenetArgs pa;
-    const int wgs = fill_forced_args(a, pa, w, c);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(c->stream);
-    e = hipMemsetAsync(a.uw, 0, (size_t)U_END * 4 + (size_t)c->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
-    if (e != hipSuccess) { taco_err("hipMemsetAsync: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    hipLaunchKernelGGL(wrnn_taco_prenet_kernel, dim3(wgs), dim3(NT), 0, stream, pa);
-    e = hipGetLastError();
-    if (e != hipSuccess) { taco_err("launch of the PreNet pre-pass (%d workgroups): %s", wgs, hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    void *params[] = {(void *)&a};
-    const void *kern = c->n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2, true> : c->n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4, true>
-                                                                                                         : (const void *)wrnn_taco_batch_kernel<8, true>;
-    e = hipLaunchCooperativeKernel(kern, dim3(R_NWG), dim3(NT), params, 0, stream);
-    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
-    return WRNN_OK;
 }
 
 // ---------------- two groups per launch ----------------
@@ -953,39 +892,46 @@ template <class Call> static int check_groups_table(const Call *const *calls, in
 }
 
 // ... and after them: what the groups of one launch must share, and what they must not
-template <class Call> static int check_groups_pair(const Call *c0, const Call *c1)
+static int check_groups_pair(const TacoCallView &c0, const TacoCallView &c1)
 {
-    if (c0->stream != c1->stream) {
-        taco_err("group 1: stream %p, group 0 has %p: the groups of a call ride ONE launch on one stream", c1->stream, c0->stream);
+    if (c0.stream != c1.stream) {
+        taco_err("group 1: stream %p, group 0 has %p: the groups of a call ride ONE launch on one stream", c1.stream, c0.stream);
         return WRNN_ERR_ARG;
     }
-    if (c0->r != c1->r || c0->max_r != c1->max_r) {
-        taco_err("group 1: r=%d max_r=%d, group 0 has r=%d max_r=%d: the groups of a call share the weights, so r and max_r are equal", c1->r, c1->max_r,
-                 c0->r, c0->max_r);
+    if (c0.r != c1.r || c0.max_r != c1.max_r) {
+        taco_err("group 1: r=%d max_r=%d, group 0 has r=%d max_r=%d: the groups of a call share the weights, so r and max_r are equal", c1.r, c1.max_r,
+                 c0.r, c0.max_r);
         return WRNN_ERR_ARG;
     }
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(c0->workspace), b1 = reinterpret_cast<uintptr_t>(c1->workspace);
-    if (b0 < b1 + c1->workspace_bytes && b1 < b0 + c0->workspace_bytes) {
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(c0.workspace), b1 = reinterpret_cast<uintptr_t>(c1.workspace);
+    if (b0 < b1 + c1.workspace_bytes && b1 < b0 + c0.workspace_bytes) {
         taco_err("the workspaces of group 0 (%zu bytes at %p) and group 1 (%zu bytes at %p) overlap: every group needs a workspace of its own",
-                 c0->workspace_bytes, c0->workspace, c1->workspace_bytes, c1->workspace);
+                 c0.workspace_bytes, c0.workspace, c1.workspace_bytes, c1.workspace);
         return WRNN_ERR_ARG;
     }
     return WRNN_OK;
 }
 
-template <bool FORCED> static const void *taco_groups_kernel(int n_sent)
+template <bool FORCED, bool GROUPED> static const void *taco_kernel(int n_sent)
 {
-    return n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2, FORCED, true> : n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4, FORCED, true>
-                                                                                             : (const void *)wrnn_taco_batch_kernel<8, FORCED, true>;
+    return n_sent <= 2 ? (const void *)wrnn_taco_batch_kernel<2, FORCED, GROUPED> : n_sent <= 4 ? (const void *)wrnn_taco_batch_kernel<4, FORCED, GROUPED>
+                                                                                                : (const void *)wrnn_taco_batch_kernel<8, FORCED, GROUPED>;
 }
 
-// The device's side of a grouped call, before anything is enqueued: G_MAX * R_NWG workgroups of one per CU must be co-resident.  The occupancy
-// query is the one the runtime's cooperative launch repeats, so a refusal is found here, with neither workspace written.
-static int taco_groups_residency(int device, const void *kern)
+// The device's side of a call, before anything is enqueued.  A plain call: R_NWG CUs.  A grouped call: G_MAX * R_NWG workgroups of one per CU
+// must be co-resident; the occupancy query is the one the runtime's cooperative launch repeats, so a refusal is found here, with neither
+// workspace written.
+static int taco_residency(int device, const void *kern, bool grouped, const char *kernel_word)
 {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) { taco_err("hipGetDeviceProperties: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    if (!grouped) {
+        if (prop.multiProcessorCount >= R_NWG) return WRNN_OK;
+        taco_err("the %s decoder kernel needs >= %d CUs (one LSTM unit per wave of %d co-resident workgroups); device has %d", kernel_word, R_NWG, R_NWG,
+                 prop.multiProcessorCount);
+        return WRNN_ERR_RESIDENCY;
+    }
     if (prop.multiProcessorCount < G_MAX * R_NWG) {
         taco_err("a launch of %d groups needs >= %d CUs (%d co-resident workgroups per group, one per CU); device has %d", G_MAX, G_MAX * R_NWG, R_NWG,
                  prop.multiProcessorCount);
@@ -1001,77 +947,69 @@ static int taco_groups_residency(int device, const void *kern)
     return WRNN_OK;
 }
 
-extern "C" int wrnn_taco_decode_batch_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *const *calls, int32_t n_groups)
+static void group_prefix(char (&pre)[16], int g, int n_groups)
 {
-    // ---- arguments: every group's are checked before the first HIP call ----
-    int bad = check_groups_table(calls, n_groups);
-    if (bad != WRNN_OK) return bad;
-    if (n_groups == 1) return wrnn_taco_decode_batch(device, w, calls[0]);
-    for (int g = 0; g < G_MAX; ++g) {
-        char pre[16];
-        snprintf(pre, sizeof pre, "group %d: ", g);
-        bad = check_batch_call(w, calls[g], pre);
+    pre[0] = 0;
+    if (n_groups > 1) snprintf(pre, sizeof pre, "group %d: ", g);
+}
+
+// One call of either form, of one group (the plain kernels on R_NWG workgroups) or of G_MAX (the GROUPED kernels): check, fill, launch.  The
+// arguments of every group, and of the pair, are checked before the first HIP call.
+template <bool FORCED, class Call> static int taco_decode(int device, const wrnn_taco_weights *w, const Call *const *calls, int n_groups)
+{
+    const bool grouped = n_groups > 1;
+    TacoCallView c[G_MAX];
+    char pre[16];
+    for (int g = 0; g < n_groups; ++g) {
+        group_prefix(pre, g, n_groups);
+        c[g] = view_of(calls[g]);
+        const int bad = check_call(w, c[g], pre);
         if (bad != WRNN_OK) return bad;
     }
-    bad = check_groups_pair(calls[0], calls[1]);
+    int bad = grouped ? check_groups_pair(c[0], c[1]) : WRNN_OK;
     if (bad != WRNN_OK) return bad;
     // ---- device ----
     DeviceGuard dg(device);
     hipError_t e = dg.err;
     if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    const int n_max = calls[0]->n_sent > calls[1]->n_sent ? calls[0]->n_sent : calls[1]->n_sent;
-    const void *kern = taco_groups_kernel<false>(n_max);
-    bad = taco_groups_residency(device, kern);
+    const int n_max = grouped && c[1].n_sent > c[0].n_sent ? c[1].n_sent : c[0].n_sent;
+    const void *kern = grouped ? taco_kernel<FORCED, true>(n_max) : taco_kernel<FORCED, false>(n_max);
+    bad = taco_residency(device, kern, grouped, c[0].words->kernel);
     if (bad != WRNN_OK) return bad;
-    TacoGroupArgs<false> ga;
-    for (int g = 0; g < G_MAX; ++g) fill_batch_args(ga.g[g], w, calls[g]);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(calls[0]->stream);
-    for (int g = 0; g < G_MAX; ++g) {
-        e = hipMemsetAsync(ga.g[g].uw, 0, (size_t)U_END * 4 + (size_t)calls[g]->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
-        if (e != hipSuccess) { taco_err("group %d: hipMemsetAsync: %s", g, hipGetErrorString(e)); return WRNN_ERR_HIP; }
+    TacoGroupArgs<FORCED> ga;                                              // (a plain call's block is ga.g[0])
+    TacoPrenetArgs pa[G_MAX];
+    int wgs[G_MAX];
+    for (int g = 0; g < n_groups; ++g) wgs[g] = fill_args<FORCED>(ga.g[g], pa[g], w, c[g]);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(c[0].stream);
+    for (int g = 0; g < n_groups; ++g) {
+        group_prefix(pre, g, n_groups);
+        e = hipMemsetAsync(ga.g[g].uw, 0, (size_t)U_END * 4 + (size_t)c[g].n_sent * BV_END * 8, stream);               // tags 0: never a step's tag
+        if (e != hipSuccess) { taco_err("%shipMemsetAsync: %s", pre, hipGetErrorString(e)); return WRNN_ERR_HIP; }
+        if constexpr (FORCED) {
+            hipLaunchKernelGGL(wrnn_taco_prenet_kernel, dim3(wgs[g]), dim3(NT), 0, stream, pa[g]);     // (one pre-pass launch per group: its table)
+            e = hipGetLastError();
+            if (e != hipSuccess) { taco_err("%slaunch of the PreNet pre-pass (%d workgroups): %s", pre, wgs[g], hipGetErrorString(e)); return WRNN_ERR_HIP; }
+        }
     }
-    void *params[] = {(void *)&ga};
-    e = hipLaunchCooperativeKernel(kern, dim3(G_MAX * R_NWG), dim3(NT), params, 0, stream);
-    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", G_MAX * R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
+    void *params[] = {grouped ? (void *)&ga : (void *)&ga.g[0]};
+    e = hipLaunchCooperativeKernel(kern, dim3(n_groups * R_NWG), dim3(NT), params, 0, stream);
+    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", n_groups * R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
     return WRNN_OK;
+}
+
+extern "C" int wrnn_taco_decode_batch(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *c) { return taco_decode<false>(device, w, &c, 1); }
+
+extern "C" int wrnn_taco_decode_forced(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *c) { return taco_decode<true>(device, w, &c, 1); }
+
+// (n_groups == 1 is the plain call: the same message, without a group in front)
+extern "C" int wrnn_taco_decode_batch_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_batch_call *const *calls, int32_t n_groups)
+{
+    const int bad = check_groups_table(calls, n_groups);
+    return bad != WRNN_OK ? bad : taco_decode<false>(device, w, calls, n_groups);
 }
 
 extern "C" int wrnn_taco_decode_forced_groups(int device, const wrnn_taco_weights *w, const wrnn_taco_forced_call *const *calls, int32_t n_groups)
 {
-    // ---- arguments: every group's are checked before the first HIP call ----
-    int bad = check_groups_table(calls, n_groups);
-    if (bad != WRNN_OK) return bad;
-    if (n_groups == 1) return wrnn_taco_decode_forced(device, w, calls[0]);
-    for (int g = 0; g < G_MAX; ++g) {
-        char pre[16];
-        snprintf(pre, sizeof pre, "group %d: ", g);
-        bad = check_forced_call(w, calls[g], pre);
-        if (bad != WRNN_OK) return bad;
-    }
-    bad = check_groups_pair(calls[0], calls[1]);
-    if (bad != WRNN_OK) return bad;
-    // ---- device ----
-    DeviceGuard dg(device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) { taco_err("hipSetDevice: %s", hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    const int n_max = calls[0]->n_sent > calls[1]->n_sent ? calls[0]->n_sent : calls[1]->n_sent;
-    const void *kern = taco_groups_kernel<true>(n_max);
-    bad = taco_groups_residency(device, kern);
-    if (bad != WRNN_OK) return bad;
-    TacoGroupArgs<true> ga;
-    TacoPrenetArgs pa[G_MAX];
-    int wgs[G_MAX];
-    for (int g = 0; g < G_MAX; ++g) wgs[g] = fill_forced_args(ga.g[g], pa[g], w, calls[g]);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(calls[0]->stream);
-    for (int g = 0; g < G_MAX; ++g) {
-        e = hipMemsetAsync(ga.g[g].uw, 0, (size_t)U_END * 4 + (size_t)calls[g]->n_sent * BV_END * 8, stream);          // tags 0: never a step's tag
-        if (e != hipSuccess) { taco_err("group %d: hipMemsetAsync: %s", g, hipGetErrorString(e)); return WRNN_ERR_HIP; }
-        hipLaunchKernelGGL(wrnn_taco_prenet_kernel, dim3(wgs[g]), dim3(NT), 0, stream, pa[g]);        // (one pre-pass launch per group: its table)
-        e = hipGetLastError();
-        if (e != hipSuccess) { taco_err("group %d: launch of the PreNet pre-pass (%d workgroups): %s", g, wgs[g], hipGetErrorString(e)); return WRNN_ERR_HIP; }
-    }
-    void *params[] = {(void *)&ga};
-    e = hipLaunchCooperativeKernel(kern, dim3(G_MAX * R_NWG), dim3(NT), params, 0, stream);
-    if (e != hipSuccess) { taco_err("cooperative launch of %d workgroups refused: %s", G_MAX * R_NWG, hipGetErrorString(e)); return WRNN_ERR_RESIDENCY; }
-    return WRNN_OK;
+    const int bad = check_groups_table(calls, n_groups);
+    return bad != WRNN_OK ? bad : taco_decode<true>(device, w, calls, n_groups);
 }

@@ -22,11 +22,14 @@ the encoder and the post-net -- embedding, pre-net, both CBHGs, `encoder_proj`, 
     m = torch.tensor(np.clip((m + 4) / 8, 0, 1)).unsqueeze(0)     # gen_tacotron.py:143-145
     voc.generate(m, path, True, 11_000, 550, True)               # gen_tacotron.py:161-163
 """
+import collections
 import re
 
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from ._lib import TACO_BATCH_MAX
 
 #: the character part of the reference's symbol table (utils/text/symbols.py:8-17: pad, '-', punctuation, letters; the ARPAbet
 #: symbols follow and are only reachable through {curly brace} input)
@@ -40,6 +43,14 @@ def text_to_ids(text):
     transliterates and spells out numbers / abbreviations (needs unidecode + inflect); for text without those both agree."""
     text = re.sub(r'\s+', ' ', text.lower())
     return [_ID[c] for c in text if c in _ID and c not in '_~']
+
+
+#: A form of the batched decoder kernel as `TacotronInference._decode_launch` drives it: the call struct, the plain and the groups entry point, the
+#: workspace attributes of the first and the second group of a launch, the form's word in an error message; the per-sentence int32 table
+#: (`count`, its values `counts(mels, S, steps, r)`) and the step limits that follow from it (`limits(counts, r)`); the table of ground-truth mels
+#: (or None); whether a sentence ends on a stop test (`steps_done`, `stop_threshold`); `workspace(L, S, table, r)` -> (bytes a call needs, None or
+#: a function for the bytes a NEW workspace gets if that is more); the ValueError text for a table the size function refuses (or None).
+_DecodeForm = collections.namedtuple('_DecodeForm', 'struct plain grouped ws_names word count counts limits mel_table stop_test refused workspace')
 
 
 class TacotronInference:
@@ -229,117 +240,96 @@ class TacotronInference:
         except Exception:
             pass
 
-    def _front_workspace(self, rows):
+    def _grow(self, name, need, first=None):
+        """The workspace kept as attribute `name` (uint8, on the device).  Where it is missing or shorter than `need` bytes it is replaced: by one
+        of `need` bytes, or of `first()` if that is more."""
+        if getattr(self, name) is None or getattr(self, name).numel() < need:
+            setattr(self, name, torch.empty(max(need, first() if first else 0), dtype=torch.uint8, device=self.device))
+        return getattr(self, name)
+
+    def _front_lib(self):
+        """(the library, the front handle) for an encoder / post-net kernel call; WrnnError where there is no handle."""
         from . import _lib
-        need = int(_lib.lib().wrnn_taco_front_workspace_bytes(self._front, rows))
-        if self._front_ws is None or self._front_ws.numel() < need:
-            self._front_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._front_ws
+        L, h = _lib.lib(), self._front_handle()
+        if h is None:
+            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
+        return L, h
+
+    def _front_workspace(self, L, h, lengths, many):
+        """(the front workspace, grown for a call over sentences of `lengths` rows; the call's count arguments: (rows,), or `many`: (the HOST
+        table of the lengths, their number)).  ValueError for a table the library refuses, before anything is uploaded or allocated."""
+        import ctypes
+        from . import _lib
+        if not many:
+            return self._grow('_front_ws', int(L.wrnn_taco_front_workspace_bytes(h, lengths[0]))), (lengths[0],)
+        n = (ctypes.c_int32 * len(lengths))(*lengths)
+        need = int(L.wrnn_taco_front_workspace_bytes_many(h, n, len(lengths)))
+        if need == 0:
+            raise ValueError(f'{len(lengths)} sentences of lengths {list(lengths)}: 1..{_lib.TACO_FRONT_MANY_MAX} sentences of 1..2^20 rows per call')
+        return self._grow('_front_ws', need), (n, len(lengths))
+
+    def _front_call(self, L, h, entry, source, count, ws, lengths, *, widths, pre_width):
+        """`entry(h, source, *count, outputs, workspace, stream)`: one encoder / post-net call over sentences of `lengths` rows.  The outputs are
+        allocated here, (rows, width) each: one per entry of `widths`, then the highway output in front of the GRU (`pre_width`; None: not
+        wanted, and None in the result).  Returns per sentence the tuple of its rows of every output.  Asynchronous on the current stream."""
+        from . import _lib
+        rows = sum(lengths)
+        outs = [torch.empty(rows, w, device=self.device) for w in widths] + [torch.empty(rows, pre_width, device=self.device) if pre_width else None]
+        rc = getattr(L, entry)(h, source, *count, *[t.data_ptr() if t is not None else None for t in outs], ws.data_ptr(), ws.numel(),
+                               torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != _lib.WRNN_OK:
+            raise _lib.WrnnError(f'{entry} failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        if len(lengths) == 1:
+            return [tuple(outs)]
+        ends = np.cumsum(lengths)
+        return [tuple(t[e - k:e] if t is not None else None for t in outs) for k, e in zip(lengths, ends.tolist())]
+
+    def _encode_run(self, ids, lengths, want_pre_rnn):
+        """`encode_kernel` (lengths None: `ids` is one sentence) / `encode_kernel_many` (`ids`: the sentences of `lengths` ids, concatenated)."""
+        L, h = self._front_lib()
+        many = lengths is not None
+        ids_h = torch.as_tensor(ids, dtype=torch.int32, device='cpu').contiguous()
+        lengths = lengths if many else [ids_h.numel()]
+        ws, count = self._front_workspace(L, h, lengths, many)                     # (a refused table: before the upload)
+        ids_d = ids_h.to(self.device)
+        D, C2 = self.p['encoder_proj.weight'].shape
+        rows = self._front_call(L, h, 'wrnn_taco_encode_many' if many else 'wrnn_taco_encode', ids_d.data_ptr(), count, ws, lengths,
+                                widths=(C2, D), pre_width=C2 // 2 if want_pre_rnn else None)
+        return [(seq.unsqueeze(0), seq_proj.unsqueeze(0), pre) for seq, seq_proj, pre in rows]
 
     def encode_kernel(self, ids, want_pre_rnn=False):
         """`encode` through `wrnn_taco_encode`: (encoder_seq (1, n, 2C), its projection (1, n, D), the highway output (n, C) in front of the
         GRU or None).  Asynchronous on the current stream."""
-        from . import _lib
-        L, h = _lib.lib(), self._front_handle()
-        if h is None:
-            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
-        dev = self.device
-        ids_d = torch.as_tensor(ids, dtype=torch.int32, device='cpu').to(dev).contiguous()
-        n = ids_d.numel()
-        seq = torch.empty(1, n, self.p['encoder_proj.weight'].shape[1], device=dev)
-        seq_proj = torch.empty(1, n, self.p['encoder_proj.weight'].shape[0], device=dev)
-        pre = torch.empty(n, seq.size(2) // 2, device=dev) if want_pre_rnn else None
-        ws = self._front_workspace(n)
-        rc = L.wrnn_taco_encode(h, ids_d.data_ptr(), n, seq.data_ptr(), seq_proj.data_ptr(), pre.data_ptr() if want_pre_rnn else None,
-                                ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_encode failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        return seq, seq_proj, pre
-
-    def postnet_kernel(self, mel, want_pre_rnn=False):
-        """The post-net CBHG and `post_proj` through `wrnn_taco_postnet`: mel (1, n_mels, N) or (n_mels, N) on the device -> (linear (N, fft),
-        the highway output (N, C) or None).  Asynchronous on the current stream."""
-        from . import _lib
-        L, h = _lib.lib(), self._front_handle()
-        if h is None:
-            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
-        dev = self.device
-        m = mel.reshape(self.n_mels, -1).to(dev, torch.float32).contiguous()
-        N = m.size(1)
-        linear = torch.empty(N, self.p['post_proj.weight'].shape[0], device=dev)
-        pre = torch.empty(N, self.p['post_proj.weight'].shape[1] // 2, device=dev) if want_pre_rnn else None
-        ws = self._front_workspace(N)
-        rc = L.wrnn_taco_postnet(h, m.data_ptr(), N, linear.data_ptr(), pre.data_ptr() if want_pre_rnn else None, ws.data_ptr(), ws.numel(),
-                                 torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_postnet failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        return linear, pre
-
-    def _front_workspace_many(self, lengths):
-        """(workspace, the HOST int32 array of `lengths`) for one `_many` call; ValueError for a table the library refuses."""
-        import ctypes
-        from . import _lib
-        n = (ctypes.c_int32 * len(lengths))(*lengths)
-        need = int(_lib.lib().wrnn_taco_front_workspace_bytes_many(self._front, n, len(lengths)))
-        if need == 0:
-            raise ValueError(f'{len(lengths)} sentences of lengths {list(lengths)}: 1..{_lib.TACO_FRONT_MANY_MAX} sentences of 1..2^20 rows per call')
-        if self._front_ws is None or self._front_ws.numel() < need:
-            self._front_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._front_ws, n
+        return self._encode_run(ids, None, want_pre_rnn)[0]
 
     def encode_kernel_many(self, list_of_ids, want_pre_rnn=False):
         """`encode_kernel` for a list of 1..64 sentences through ONE `wrnn_taco_encode_many` call (one host-to-device copy of the concatenated
         ids, every stage one launch for all sentences).  Returns per sentence (encoder_seq (1, n, 2C), its projection (1, n, D), the highway
         output (n, C) or None): views of the call's concatenated outputs, each bit-identical to `encode_kernel` of that sentence alone.
         Asynchronous on the current stream."""
-        from . import _lib
-        L, h = _lib.lib(), self._front_handle()
-        if h is None:
-            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
-        dev = self.device
-        lengths = [len(ids) for ids in list_of_ids]
-        ws, n = self._front_workspace_many(lengths)
-        rows = sum(lengths)
-        ids_d = torch.as_tensor([int(i) for ids in list_of_ids for i in ids], dtype=torch.int32, device='cpu').to(dev)
-        seq = torch.empty(rows, self.p['encoder_proj.weight'].shape[1], device=dev)
-        seq_proj = torch.empty(rows, self.p['encoder_proj.weight'].shape[0], device=dev)
-        pre = torch.empty(rows, seq.size(1) // 2, device=dev) if want_pre_rnn else None
-        rc = L.wrnn_taco_encode_many(h, ids_d.data_ptr(), n, len(lengths), seq.data_ptr(), seq_proj.data_ptr(), pre.data_ptr() if want_pre_rnn else None,
-                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_encode_many failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        out, o = [], 0
-        for k in lengths:
-            out.append((seq[o:o + k].unsqueeze(0), seq_proj[o:o + k].unsqueeze(0), pre[o:o + k] if want_pre_rnn else None))
-            o += k
-        return out
+        return self._encode_run([int(i) for ids in list_of_ids for i in ids], [len(ids) for ids in list_of_ids], want_pre_rnn)
+
+    def _postnet_run(self, list_of_mels, many, want_pre_rnn):
+        import ctypes
+        L, h = self._front_lib()
+        ms = [mel.reshape(self.n_mels, -1).to(self.device, torch.float32).contiguous() for mel in list_of_mels]
+        lengths = [m.size(1) for m in ms]
+        ws, count = self._front_workspace(L, h, lengths, many)
+        source = (ctypes.c_void_p * len(ms))(*[m.data_ptr() for m in ms]) if many else ms[0].data_ptr()
+        fft, C2 = self.p['post_proj.weight'].shape
+        return self._front_call(L, h, 'wrnn_taco_postnet_many' if many else 'wrnn_taco_postnet', source, count, ws, lengths,
+                                widths=(fft,), pre_width=C2 // 2 if want_pre_rnn else None)
+
+    def postnet_kernel(self, mel, want_pre_rnn=False):
+        """The post-net CBHG and `post_proj` through `wrnn_taco_postnet`: mel (1, n_mels, N) or (n_mels, N) on the device -> (linear (N, fft),
+        the highway output (N, C) or None).  Asynchronous on the current stream."""
+        return self._postnet_run([mel], False, want_pre_rnn)[0]
 
     def postnet_kernel_many(self, list_of_mels, want_pre_rnn=False):
         """`postnet_kernel` for a list of 1..64 mels ((1, n_mels, N_s) or (n_mels, N_s) each) through ONE `wrnn_taco_postnet_many` call.  Returns per
         sentence (linear (N_s, fft), the highway output (N_s, C) or None): views of the call's concatenated outputs, each bit-identical to
         `postnet_kernel` of that mel alone.  Asynchronous on the current stream."""
-        import ctypes
-        from . import _lib
-        L, h = _lib.lib(), self._front_handle()
-        if h is None:
-            raise _lib.WrnnError(f'wrnn_taco_front_create refused these dims: {getattr(self, "_front_refused", "unsupported state dict")}')
-        dev = self.device
-        ms = [mel.reshape(self.n_mels, -1).to(dev, torch.float32).contiguous() for mel in list_of_mels]
-        lengths = [m.size(1) for m in ms]
-        ws, n = self._front_workspace_many(lengths)
-        rows = sum(lengths)
-        linear = torch.empty(rows, self.p['post_proj.weight'].shape[0], device=dev)
-        pre = torch.empty(rows, self.p['post_proj.weight'].shape[1] // 2, device=dev) if want_pre_rnn else None
-        ptrs = (ctypes.c_void_p * len(ms))(*[m.data_ptr() for m in ms])
-        rc = L.wrnn_taco_postnet_many(h, ptrs, n, len(ms), linear.data_ptr(), pre.data_ptr() if want_pre_rnn else None, ws.data_ptr(), ws.numel(),
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _lib.WRNN_OK:
-            raise _lib.WrnnError(f'wrnn_taco_postnet_many failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        out, o = [], 0
-        for k in lengths:
-            out.append((linear[o:o + k], pre[o:o + k] if want_pre_rnn else None))
-            o += k
-        return out
+        return self._postnet_run(list_of_mels, True, want_pre_rnn)
 
     def encode(self, ids):
         """Encoder (:24-39) + `encoder_proj` (:403-404): ids (n,) -> encoder_seq (1, n, 2C), its projection (1, n, D)."""
@@ -389,24 +379,6 @@ class TacotronInference:
         if dev.type != 'cuda':
             raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
         L = _lib.lib()
-        p, q = self.p, 'decoder.'
-        names = dict(prenet_fc1_w='prenet.fc1.weight', prenet_fc1_b='prenet.fc1.bias', prenet_fc2_w='prenet.fc2.weight',
-                     prenet_fc2_b='prenet.fc2.bias', attn_rnn_w_ih='attn_rnn.weight_ih', attn_rnn_w_hh='attn_rnn.weight_hh',
-                     attn_rnn_b_ih='attn_rnn.bias_ih', attn_rnn_b_hh='attn_rnn.bias_hh', attn_W_w='attn_net.W.weight',
-                     attn_W_b='attn_net.W.bias', attn_conv_w='attn_net.conv.weight', attn_L_w='attn_net.L.weight',
-                     attn_L_b='attn_net.L.bias', attn_v_w='attn_net.v.weight', rnn_input_w='rnn_input.weight',
-                     rnn_input_b='rnn_input.bias', rnn1_w_ih='res_rnn1.weight_ih', rnn1_w_hh='res_rnn1.weight_hh',
-                     rnn1_b_ih='res_rnn1.bias_ih', rnn1_b_hh='res_rnn1.bias_hh', rnn2_w_ih='res_rnn2.weight_ih',
-                     rnn2_w_hh='res_rnn2.weight_hh', rnn2_b_ih='res_rnn2.bias_ih', rnn2_b_hh='res_rnn2.bias_hh',
-                     mel_proj_w='mel_proj.weight')
-        keep = {k: p[q + v].detach().to(dev, torch.float32).contiguous() for k, v in names.items()}
-        w = _lib.TacoWeights()
-        w.struct_bytes = ctypes.sizeof(_lib.TacoWeights)
-        w.n_mels, w.prenet1, w.prenet2 = self.n_mels, keep['prenet_fc1_w'].shape[0], keep['prenet_fc2_w'].shape[0]
-        w.decoder_dims, w.encoder_width, w.lstm_dims = self.decoder_dims, seq.size(2), self.lstm_dims
-        w.attn_filters, w.attn_kernel = keep['attn_conv_w'].shape[0], keep['attn_conv_w'].shape[2]
-        for k, tns in keep.items():
-            setattr(w, k, tns.data_ptr())
         n = seq.size(1)
         max_steps = (steps + self.r - 1) // self.r
         seq_c, proj_c = seq[0].contiguous(), seq_proj[0].contiguous()
@@ -421,7 +393,7 @@ class TacotronInference:
         c.steps_done, c.workspace, c.workspace_bytes = done.data_ptr(), ws.data_ptr(), ws.numel()
         c.stream = torch.cuda.current_stream(dev).cuda_stream
         c.variant = int(variant)
-        rc = L.wrnn_taco_decode((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(w), ctypes.byref(c))
+        rc = L.wrnn_taco_decode((dev.index if dev.index is not None else torch.cuda.current_device()), ctypes.byref(self.decoder_weights()), ctypes.byref(c))
         if rc != _lib.WRNN_OK:
             raise _lib.WrnnError(f'wrnn_taco_decode failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
         st4 = (ctypes.c_uint32 * 4)()
@@ -460,6 +432,92 @@ class TacotronInference:
             self._dec_w = (w, keep)
         return self._dec_w[0]
 
+    # The two forms of the batched decoder kernel as `_decode_launch` drives them (`_DecodeForm`, above).
+    _FREE = _DecodeForm(
+        struct='TacoBatchCall', plain='wrnn_taco_decode_batch', grouped='wrnn_taco_decode_batch_groups', ws_names=('_batch_ws', '_batch_ws2'),
+        word='batched', count='max_steps', counts=lambda mels, S, steps, r: [(steps + r - 1) // r] * S, limits=lambda counts, r: counts,
+        mel_table=None, stop_test=True, refused=None,
+        # (a new workspace holds at least the full batch of that many sentences)
+        workspace=lambda L, S, table, r: (L.wrnn_taco_batch_workspace_bytes(S), lambda: int(L.wrnn_taco_batch_workspace_bytes(min(TACO_BATCH_MAX, max(S, 1))))))
+    _FORCED = _DecodeForm(
+        struct='TacoForcedCall', plain='wrnn_taco_decode_forced', grouped='wrnn_taco_decode_forced_groups', ws_names=('_forced_ws', '_forced_ws2'),
+        word='forced', count='frames', counts=lambda mels, S, steps, r: [m.size(1) for m in mels],
+        limits=lambda counts, r: [(k + r - 1) // r for k in counts], mel_table='force_mel', stop_test=False,
+        refused='{S} sentences of {counts} frames at r={r}: 1..%d sentences of 1..2^20 frames per call' % TACO_BATCH_MAX,
+        workspace=lambda L, S, table, r: (L.wrnn_taco_forced_workspace_bytes(S, table, r), None))
+
+    def _decode_launch(self, form, groups, steps=None):
+        """The decoder loops of ONE or TWO groups of sentences in the form `form`.  A group is (encs, mels): encs as `_decode_batch_kernel` takes
+        them; mels the ground-truth mels of `_FORCED` (a sentence runs ceil(frames / r) steps), None for `_FREE` (every sentence runs at most
+        ceil(steps / r) steps and ends on its own stop test).  One group: the plain entry point.  Two: ONE launch of the groups entry point, a
+        group on each half of a 256-CU device, every group with a workspace of its own (for `_FORCED`, a pre-pass per group in front); where
+        the device refuses the 256 co-resident workgroups (WRNN_ERR_RESIDENCY, nothing written) the groups take the plain call one after the
+        other.  Returns the groups' results in order; `last_decode_groups` gains one entry per native call."""
+        import ctypes
+        from . import _lib
+        dev, r = self.device, self.r
+        if dev.type != 'cuda':
+            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
+        if not 1 <= len(groups) <= _lib.TACO_GROUPS_MAX:
+            raise ValueError(f'{len(groups)} groups: a launch decodes 1..{_lib.TACO_GROUPS_MAX}')
+        L, plain, grouped, word = _lib.lib(), form.plain, form.grouped, form.word
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+        calls = []
+        for ws_name, (encs, mels) in zip(form.ws_names, groups):
+            S = len(encs)
+            seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
+            projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
+            mels = [m.contiguous() for m in mels] if form.mel_table else None
+            counts = form.counts(mels, S, steps, r)
+            limits = form.limits(counts, r)
+            table = (ctypes.c_int32 * S)(*counts)
+            need, first = form.workspace(L, S, table, r)
+            if need == 0 and form.refused:
+                raise ValueError(form.refused.format(S=S, counts=counts, r=r))
+            ws = self._grow(ws_name, int(need), first)
+            outs = [torch.zeros(k, self.n_mels, r, device=dev) for k in limits]
+            scores = [torch.zeros(k, q.size(0), device=dev) for k, q in zip(limits, seqs)]
+            done = torch.zeros(S, dtype=torch.int32, device=dev) if form.stop_test else None   # (None: a sentence runs all its steps)
+            c = getattr(_lib, form.struct)()
+            c.struct_bytes = ctypes.sizeof(c)
+            c.n_sent, c.r, c.max_r = S, r, self.max_r
+            c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
+            setattr(c, form.count, table)
+            if form.stop_test:
+                c.steps_done, c.stop_threshold = done.data_ptr(), self.stop_threshold
+            for field, ts in ((form.mel_table, mels), ('seq', seqs), ('seq_proj', projs), ('mel_out', outs), ('scores_out', scores)):
+                if field:
+                    setattr(c, field, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
+            c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+            c.stream = torch.cuda.current_stream(dev).cuda_stream
+            calls.append((c, ws, outs, scores, limits, done, (seqs, projs, mels)))
+
+        def finish(call):
+            c, ws, outs, scores, limits, done, _ = call
+            st4 = (ctypes.c_uint32 * 4)()
+            rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
+            if rc != _lib.WRNN_OK or st4[0] != 0:
+                raise _lib.WrnnError(f'Tacotron {word} decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
+            ks = limits if done is None else [int(k) for k in done.cpu()]
+            return [(m[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * r), a[:k]) for m, a, k in zip(outs, scores, ks)]
+
+        if len(calls) == 2:
+            table = (ctypes.POINTER(getattr(_lib, form.struct)) * 2)(*[ctypes.pointer(call[0]) for call in calls])
+            rc = getattr(L, grouped)(device, ctypes.byref(self.decoder_weights()), table, 2)
+            if rc == _lib.WRNN_OK:
+                self.last_decode_groups.append(tuple(len(g[0]) for g in groups))
+                return [finish(call) for call in calls]
+            if rc != _lib.ERR_RESIDENCY:
+                raise _lib.WrnnError(f'{grouped} failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+        out = []
+        for call, g in zip(calls, groups):
+            rc = getattr(L, plain)(device, ctypes.byref(self.decoder_weights()), ctypes.byref(call[0]))
+            if rc != _lib.WRNN_OK:
+                raise _lib.WrnnError(f'{plain} failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
+            self.last_decode_groups.append((len(g[0]),))
+            out.append(finish(call))
+        return out
+
     def _decode_batch_kernel(self, encs, steps):
         """The decoder loops of up to `_lib.TACO_BATCH_MAX` sentences in ONE persistent kernel (`wrnn_taco_decode_batch`,
         csrc/wrnn_taco_batch.hip).  encs: [(seq (1, n, 256), seq_proj (1, n, 256))], every n <= `_lib.TACO_BATCH_NMAX`.  Returns
@@ -467,70 +525,9 @@ class TacotronInference:
         return self._decode_batch_launch([encs], steps)[0]
 
     def _decode_batch_launch(self, groups, steps):
-        """The decoder loops of ONE or TWO groups of sentences (each as `_decode_batch_kernel` takes them).  One group: `wrnn_taco_decode_batch`.
-        Two: ONE `wrnn_taco_decode_batch_groups` launch, a group on each half of a 256-CU device, every group with a workspace of its own; where
-        the device refuses the 256 co-resident workgroups (WRNN_ERR_RESIDENCY, nothing written) the two groups take the plain call one after the
-        other.  Returns the groups' results in order; `last_decode_groups` gains one entry per native call."""
-        import ctypes
-        from . import _lib
-        dev = self.device
-        if dev.type != 'cuda':
-            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
-        L = _lib.lib()
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        max_steps = (steps + self.r - 1) // self.r
-        calls = []
-        for slot, encs in enumerate(groups):
-            S = len(encs)
-            seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
-            projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
-            mels = [torch.zeros(max_steps, self.n_mels, self.r, device=dev) for _ in encs]
-            scores = [torch.zeros(max_steps, q.size(0), device=dev) for q in seqs]
-            done = torch.zeros(S, dtype=torch.int32, device=dev)
-            need = int(L.wrnn_taco_batch_workspace_bytes(S))
-            name = '_batch_ws' if slot == 0 else '_batch_ws2'
-            if getattr(self, name) is None or getattr(self, name).numel() < need:
-                setattr(self, name, torch.empty(max(need, int(L.wrnn_taco_batch_workspace_bytes(min(_lib.TACO_BATCH_MAX, max(S, 1))))), dtype=torch.uint8,
-                                                device=dev))
-            ws = getattr(self, name)
-            c = _lib.TacoBatchCall()
-            c.struct_bytes = ctypes.sizeof(_lib.TacoBatchCall)
-            c.n_sent, c.r, c.max_r, c.stop_threshold = S, self.r, self.max_r, self.stop_threshold
-            c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
-            c.max_steps = (ctypes.c_int32 * S)(*([max_steps] * S))
-            for field, ts in (('seq', seqs), ('seq_proj', projs), ('mel_out', mels), ('scores_out', scores)):
-                setattr(c, field, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
-            c.steps_done, c.workspace, c.workspace_bytes = done.data_ptr(), ws.data_ptr(), ws.numel()
-            c.stream = torch.cuda.current_stream(dev).cuda_stream
-            calls.append((c, ws, mels, scores, done, (seqs, projs)))
-
-        def finish(call):
-            c, ws, mels, scores, done, _ = call
-            st4 = (ctypes.c_uint32 * 4)()
-            rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
-            if rc != _lib.WRNN_OK or st4[0] != 0:
-                raise _lib.WrnnError(f'Tacotron batched decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
-            ks = [int(k) for k in done.cpu()]
-            return [(m[:k].permute(1, 0, 2).reshape(1, self.n_mels, k * self.r), a[:k]) for m, a, k in zip(mels, scores, ks)]
-
-        if len(calls) == 2:
-            table = (ctypes.POINTER(_lib.TacoBatchCall) * 2)(*[ctypes.pointer(call[0]) for call in calls])
-            rc = L.wrnn_taco_decode_batch_groups(device, ctypes.byref(self.decoder_weights()), table, 2)
-            if rc == _lib.WRNN_OK:
-                self.last_decode_groups.append(tuple(len(g) for g in groups))
-                return [finish(call) for call in calls]
-            if rc != _lib.ERR_RESIDENCY:
-                raise _lib.WrnnError(f'wrnn_taco_decode_batch_groups failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        elif len(calls) != 1:
-            raise ValueError(f'{len(calls)} groups: a launch decodes 1..{_lib.TACO_GROUPS_MAX}')
-        out = []
-        for call, g in zip(calls, groups):
-            rc = L.wrnn_taco_decode_batch(device, ctypes.byref(self.decoder_weights()), ctypes.byref(call[0]))
-            if rc != _lib.WRNN_OK:
-                raise _lib.WrnnError(f'wrnn_taco_decode_batch failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-            self.last_decode_groups.append((len(g),))
-            out.append(finish(call))
-        return out
+        """`_decode_launch` for ONE or TWO groups of free-running sentences (each as `_decode_batch_kernel` takes them): `wrnn_taco_decode_batch`,
+        or ONE `wrnn_taco_decode_batch_groups` launch."""
+        return self._decode_launch(self._FREE, [(encs, None) for encs in groups], steps)
 
     @staticmethod
     def _pair_groups(groups, n):
@@ -539,6 +536,73 @@ class TacotronInference:
         if isinstance(n, bool) or n not in (1, 2):
             raise ValueError(f'groups={n!r}: 1 (one group of sentences per launch) or 2 (two, on a device of 256 CUs)')
         return [groups[i:i + n] for i in range(0, len(groups), n)]
+
+    # -- what generate / forward_gta and their batch forms share around the decoder -------------------------------------------------
+    def _front_path(self, kernel, cbhg_kernel):
+        """Where the encoder and the post-net run: True for `wrnn_taco_encode` / `wrnn_taco_postnet` (cbhg_kernel, and a state dict
+        `wrnn_taco_front_create` takes), False for the torch ops -- with the CBHGs' GRUs as `wrnn_bigru` where `kernel` says so."""
+        if cbhg_kernel and self.device.type != 'cuda':
+            from . import _lib
+            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
+        self._bigru_kernel = bool(kernel) and self.device.type == 'cuda'           # the CBHGs' GRUs as persistent kernels too
+        front = bool(cbhg_kernel) and self._front_handle() is not None
+        self.last_front_path = 'hip' if front else 'torch'
+        return front
+
+    def _postnet(self, mel, front):
+        """The post-net CBHG and `post_proj` (:416-421) over a decoded mel (1, n_mels, N): linear (fft, N), a device tensor."""
+        if front:
+            return self.postnet_kernel(mel)[0].transpose(0, 1)
+        return F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+
+    def _check_batch(self, max_batch, groups):
+        from . import _lib
+        if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
+            raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
+        self._pair_groups([], groups)                                              # (ValueError for anything but 1 or 2)
+
+    def _batch_frame(self, list_of_ids, front, groups, form_groups, decode, decode_long):
+        """`generate_batch` and `forward_gta_batch` behind their argument checks: encode all sentences, decode those of at most
+        `_lib.TACO_BATCH_NMAX` ids in groups -- `form_groups(their indices)` forms the groups, `_pair_groups` the launches, and
+        `decode(encs, launch)` returns the results of a launch's one or two groups -- and the others through `decode_long(i, enc)`, then run the
+        post-net.  Returns per sentence numpy (mel, linear, attention)."""
+        from . import _lib
+        M = _lib.TACO_FRONT_MANY_MAX
+        if front:
+            # all sentences side by side, <= 64 per call; a call of ONE sentence goes through the single-sentence entry point (the same bits; the
+            # sentence table costs 1-2 % there: DESIGN.md section 6)
+            enc_many = lambda chunk: self.encode_kernel_many(chunk) if len(chunk) > 1 else [self.encode_kernel(chunk[0])]
+            post_many = lambda chunk: self.postnet_kernel_many(chunk) if len(chunk) > 1 else [self.postnet_kernel(chunk[0])]
+            encs = [e[:2] for c in range(0, len(list_of_ids), M) for e in enc_many(list_of_ids[c:c + M])]
+        else:
+            encs = [self.encode(ids) for ids in list_of_ids]
+        decoded = [None] * len(encs)
+        self.last_decode_groups = []
+        for launch in self._pair_groups(form_groups([i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]), groups):
+            for group, result in zip(launch, decode(encs, launch)):
+                for i, d in zip(group, result):
+                    decoded[i] = d
+        for i, e in enumerate(encs):
+            if decoded[i] is None:
+                decoded[i] = decode_long(i, e)
+        out = []
+        if not front:
+            for mel, attn in decoded:
+                linear = self._postnet(mel, False)
+                out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
+            return out
+        # one post-net pass over all decoded mels (<= 64 per call), then ONE transfer: every result flattened into one device buffer
+        mels = [d[0] for d in decoded]
+        lins = [l for c in range(0, len(mels), M) for l, _ in post_many(mels[c:c + M])]
+        parts = [t.reshape(-1) for (mel, attn), lin in zip(decoded, lins) for t in (mel[0], lin, attn)]
+        flat, o = torch.cat(parts).cpu().numpy() if parts else None, 0
+        for (mel, attn), lin in zip(decoded, lins):
+            trio = []
+            for t in (mel[0], lin, attn):
+                trio.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
+                o += t.numel()
+            out.append((trio[0], trio[1].T, trio[2]))                              # linear (fft, N), as `generate()` returns it
+        return out
 
     @torch.no_grad()
     def generate_batch(self, list_of_ids, steps=2000, kernel=True, cbhg_kernel=False, max_batch=8, groups=1):
@@ -555,61 +619,19 @@ class TacotronInference:
         groups=2 (opt-in; a device of 256 CUs): consecutive decoder groups ride in pairs on ONE `wrnn_taco_decode_batch_groups` launch, a group on
         each half of the device -- 2 x `max_batch` sentences per launch, the same bits; an odd group out takes the plain call, and so do both
         groups of a pair where the device refuses the launch.  `last_decode_groups` lists what ran: per native call, its groups' sizes."""
-        from . import _lib
         if not kernel:
             return [self.generate(ids, steps=steps, kernel=False, cbhg_kernel=cbhg_kernel) for ids in list_of_ids]
-        if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
-            raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
-        self._pair_groups([], groups)                                              # (ValueError for anything but 1 or 2)
-        dev = self.device
-        if dev.type != 'cuda':
+        self._check_batch(max_batch, groups)
+        if self.device.type != 'cuda':
+            from . import _lib
             raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
-        self._bigru_kernel = True
-        front = bool(cbhg_kernel) and self._front_handle() is not None
-        self.last_front_path = 'hip' if front else 'torch'
-        M = _lib.TACO_FRONT_MANY_MAX
-        if front:
-            # all sentences side by side, <= 64 per call; a call of ONE sentence goes through the single-sentence entry point (the same bits; the
-            # sentence table costs 1-2 % there: DESIGN.md section 6)
-            enc_many = lambda chunk: self.encode_kernel_many(chunk) if len(chunk) > 1 else [self.encode_kernel(chunk[0])]
-            post_many = lambda chunk: self.postnet_kernel_many(chunk) if len(chunk) > 1 else [self.postnet_kernel(chunk[0])]
-            encs = [e[:2] for c in range(0, len(list_of_ids), M) for e in enc_many(list_of_ids[c:c + M])]
-        else:
-            encs = [self.encode(ids) for ids in list_of_ids]
-        decoded = [None] * len(encs)
-        short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
-        self.last_decode_groups = []
-        for launch in self._pair_groups([short[g:g + int(max_batch)] for g in range(0, len(short), int(max_batch))], groups):
-            if len(launch) == 1:
-                results = [self._decode_batch_kernel([encs[i] for i in launch[0]], steps)]
-            else:
-                results = self._decode_batch_launch([[encs[i] for i in group] for group in launch], steps)
-            for group, result in zip(launch, results):
-                for i, d in zip(group, result):
-                    decoded[i] = d
-        if front:
-            for i, e in enumerate(encs):
-                if decoded[i] is None:
-                    decoded[i] = self._decode_kernel(e[0], e[1], steps)
-            # one post-net pass over all decoded mels (<= 64 per call), then ONE transfer: every result flattened into one device buffer
-            mels = [d[0] for d in decoded]
-            lins = [l for c in range(0, len(mels), M) for l, _ in post_many(mels[c:c + M])]
-            parts = [t.reshape(-1) for (mel, attn), lin in zip(decoded, lins) for t in (mel[0], lin, attn)]
-            flat = torch.cat(parts).cpu().numpy() if parts else None
-            out, o = [], 0
-            for (mel, attn), lin in zip(decoded, lins):
-                trio = []
-                for t in (mel[0], lin, attn):
-                    trio.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
-                    o += t.numel()
-                out.append((trio[0], trio[1].T, trio[2]))                          # linear (fft, N), as `generate()` returns it
-            return out
-        out = []
-        for i, e in enumerate(encs):
-            mel, attn = decoded[i] if decoded[i] is not None else self._decode_kernel(e[0], e[1], steps)
-            linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
-            out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
-        return out
+        B = int(max_batch)
+
+        def decode(encs, launch):
+            g = [[encs[i] for i in group] for group in launch]
+            return [self._decode_batch_kernel(g[0], steps)] if len(g) == 1 else self._decode_batch_launch(g, steps)
+        return self._batch_frame(list_of_ids, self._front_path(True, cbhg_kernel), groups, lambda short: [short[g:g + B] for g in range(0, len(short), B)],
+                                 decode, lambda i, e: self._decode_kernel(e[0], e[1], steps))
 
     # -- ground-truth-aligned mels: the teacher-forced decoder ------------------------------------------------------------------
     def _forced_mel(self, mel):
@@ -644,71 +666,9 @@ class TacotronInference:
         return self._decode_forced_launch([(encs, mels)])[0]
 
     def _decode_forced_launch(self, groups):
-        """The teacher-forced loops of ONE or TWO groups, each an (encs, mels) pair as `_decode_forced_kernel` takes it.  One group:
-        `wrnn_taco_decode_forced`.  Two: ONE `wrnn_taco_decode_forced_groups` launch (a pre-pass per group, then both loops on the halves of a
-        256-CU device), every group with a workspace of its own; on WRNN_ERR_RESIDENCY (nothing written) the groups take the plain call one
-        after the other.  Returns the groups' results in order; `last_decode_groups` gains one entry per native call."""
-        import ctypes
-        from . import _lib
-        dev = self.device
-        if dev.type != 'cuda':
-            raise _lib.WrnnError('the Tacotron decoder kernel needs a HIP device (no CPU fallback)')
-        L, r = _lib.lib(), self.r
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-        calls = []
-        for slot, (encs, mels) in enumerate(groups):
-            S = len(encs)
-            seqs = [e[0][0].to(torch.float32).contiguous() for e in encs]
-            projs = [e[1][0].to(torch.float32).contiguous() for e in encs]
-            mels = [m.contiguous() for m in mels]
-            steps = [(m.size(1) + r - 1) // r for m in mels]
-            outs = [torch.zeros(k, self.n_mels, r, device=dev) for k in steps]
-            scores = [torch.zeros(k, q.size(0), device=dev) for k, q in zip(steps, seqs)]
-            frames = (ctypes.c_int32 * S)(*[m.size(1) for m in mels])
-            need = int(L.wrnn_taco_forced_workspace_bytes(S, frames, r))
-            if need == 0:
-                raise ValueError(f'{S} sentences of {list(frames)} frames at r={r}: 1..{_lib.TACO_BATCH_MAX} sentences of 1..2^20 frames per call')
-            name = '_forced_ws' if slot == 0 else '_forced_ws2'
-            if getattr(self, name) is None or getattr(self, name).numel() < need:
-                setattr(self, name, torch.empty(need, dtype=torch.uint8, device=dev))
-            ws = getattr(self, name)
-            c = _lib.TacoForcedCall()
-            c.struct_bytes = ctypes.sizeof(_lib.TacoForcedCall)
-            c.n_sent, c.r, c.max_r = S, r, self.max_r
-            c.n = (ctypes.c_int32 * S)(*[q.size(0) for q in seqs])
-            c.frames = frames
-            for field, ts in (('seq', seqs), ('seq_proj', projs), ('force_mel', mels), ('mel_out', outs), ('scores_out', scores)):
-                setattr(c, field, (ctypes.c_void_p * S)(*[t.data_ptr() for t in ts]))
-            c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
-            c.stream = torch.cuda.current_stream(dev).cuda_stream
-            calls.append((c, ws, outs, scores, steps, (seqs, projs, mels)))
-
-        def finish(call):
-            c, ws, outs, scores, steps, _ = call
-            st4 = (ctypes.c_uint32 * 4)()
-            rc = L.wrnn_taco_status(ws.data_ptr(), ctypes.byref(st4), c.stream)
-            if rc != _lib.WRNN_OK or st4[0] != 0:
-                raise _lib.WrnnError(f'Tacotron forced decoder kernel failed: status {list(st4)} {L.wrnn_taco_last_error().decode()}')
-            return [(m.permute(1, 0, 2).reshape(1, self.n_mels, k * r), a) for m, a, k in zip(outs, scores, steps)]
-
-        if len(calls) == 2:
-            table = (ctypes.POINTER(_lib.TacoForcedCall) * 2)(*[ctypes.pointer(call[0]) for call in calls])
-            rc = L.wrnn_taco_decode_forced_groups(device, ctypes.byref(self.decoder_weights()), table, 2)
-            if rc == _lib.WRNN_OK:
-                self.last_decode_groups.append(tuple(len(g[0]) for g in groups))
-                return [finish(call) for call in calls]
-            if rc != _lib.ERR_RESIDENCY:
-                raise _lib.WrnnError(f'wrnn_taco_decode_forced_groups failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-        elif len(calls) != 1:
-            raise ValueError(f'{len(calls)} groups: a launch decodes 1..{_lib.TACO_GROUPS_MAX}')
-        out = []
-        for call, g in zip(calls, groups):
-            rc = L.wrnn_taco_decode_forced(device, ctypes.byref(self.decoder_weights()), ctypes.byref(call[0]))
-            if rc != _lib.WRNN_OK:
-                raise _lib.WrnnError(f'wrnn_taco_decode_forced failed (rc={rc}): {L.wrnn_taco_last_error().decode()}')
-            self.last_decode_groups.append((len(g[0]),))
-            out.append(finish(call))
-        return out
+        """`_decode_launch` for ONE or TWO teacher-forced groups, each an (encs, mels) pair as `_decode_forced_kernel` takes it:
+        `wrnn_taco_decode_forced`, or ONE `wrnn_taco_decode_forced_groups` launch."""
+        return self._decode_launch(self._FORCED, groups)
 
     @staticmethod
     def _gta_groups(steps, max_batch):
@@ -733,13 +693,7 @@ class TacotronInference:
         norms); this is the eval form the signature offers, the only deterministic one.  PADDING: the reference pads a batch's texts with zeros
         and attends over the padding, so an utterance's features depend on its batch companions; here every sentence is decoded as if alone
         (the reference at batch size 1)."""
-        dev = self.device
-        if cbhg_kernel and dev.type != 'cuda':
-            from . import _lib
-            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
-        self._bigru_kernel = bool(kernel) and dev.type == 'cuda'
-        front = bool(cbhg_kernel) and self._front_handle() is not None
-        self.last_front_path = 'hip' if front else 'torch'
+        front = self._front_path(kernel, cbhg_kernel)
         m = self._forced_mel(mel)
         seq, seq_proj = self.encode_kernel(ids)[:2] if front else self.encode(ids)
         if kernel:
@@ -749,10 +703,7 @@ class TacotronInference:
             gta, attn = self._decode_forced_kernel([(seq, seq_proj)], [m])[0]
         else:
             gta, attn = self._decode_forced_eager(seq, seq_proj, m)
-        if front:
-            linear = self.postnet_kernel(gta)[0].transpose(0, 1)
-        else:
-            linear = F.linear(self._cbhg(gta, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
+        linear = self._postnet(gta, front)
         return gta[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()
 
     @torch.no_grad()
@@ -770,61 +721,23 @@ class TacotronInference:
 
         groups=2 (opt-in; a device of 256 CUs): consecutive groups of the sorted order ride in pairs on ONE `wrnn_taco_decode_forced_groups`
         launch, as in `generate_batch`; `last_decode_groups` lists what ran."""
-        from . import _lib
         if len(list_of_ids) != len(list_of_mels):
             raise ValueError(f'{len(list_of_ids)} id lists for {len(list_of_mels)} mels')
         if not kernel:
             return [self.forward_gta(ids, mel, kernel=False, cbhg_kernel=cbhg_kernel) for ids, mel in zip(list_of_ids, list_of_mels)]
-        if not 1 <= int(max_batch) <= _lib.TACO_BATCH_MAX:
-            raise ValueError(f'max_batch={max_batch}: 1..{_lib.TACO_BATCH_MAX}')
-        self._pair_groups([], groups)                                              # (ValueError for anything but 1 or 2)
-        dev = self.device
-        if cbhg_kernel and dev.type != 'cuda':
-            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
-        self._bigru_kernel = dev.type == 'cuda'
-        front = bool(cbhg_kernel) and self._front_handle() is not None
-        self.last_front_path = 'hip' if front else 'torch'
-        M = _lib.TACO_FRONT_MANY_MAX
+        self._check_batch(max_batch, groups)
+        front = self._front_path(True, cbhg_kernel)
         ms = [self._forced_mel(mel) for mel in list_of_mels]
-        if front:
-            enc_many = lambda chunk: self.encode_kernel_many(chunk) if len(chunk) > 1 else [self.encode_kernel(chunk[0])]
-            post_many = lambda chunk: self.postnet_kernel_many(chunk) if len(chunk) > 1 else [self.postnet_kernel(chunk[0])]
-            encs = [e[:2] for c in range(0, len(list_of_ids), M) for e in enc_many(list_of_ids[c:c + M])]
-        else:
-            encs = [self.encode(ids) for ids in list_of_ids]
-        decoded = [None] * len(encs)
-        short = [i for i, e in enumerate(encs) if e[0].size(1) <= _lib.TACO_BATCH_NMAX]
-        steps = [(ms[i].size(1) + self.r - 1) // self.r for i in short]
-        self.last_decode_groups = []
-        for launch in self._pair_groups([[short[j] for j in group] for group in self._gta_groups(steps, int(max_batch))], groups):
-            if len(launch) == 1:
-                results = [self._decode_forced_kernel([encs[i] for i in launch[0]], [ms[i] for i in launch[0]])]
-            else:                                                                  # neighbours in the order of step counts: they end together
-                results = self._decode_forced_launch([([encs[i] for i in idx], [ms[i] for i in idx]) for idx in launch])
-            for idx, result in zip(launch, results):
-                for i, d in zip(idx, result):
-                    decoded[i] = d
-        for i, e in enumerate(encs):
-            if decoded[i] is None:                                                 # more than 256 ids: the eager loop on the device
-                decoded[i] = self._decode_forced_eager(e[0], e[1], ms[i])
-        if front:
-            mels = [d[0] for d in decoded]
-            lins = [l for c in range(0, len(mels), M) for l, _ in post_many(mels[c:c + M])]
-            parts = [t.reshape(-1) for (mel, attn), lin in zip(decoded, lins) for t in (mel[0], lin, attn)]
-            flat = torch.cat(parts).cpu().numpy() if parts else None
-            out, o = [], 0
-            for (mel, attn), lin in zip(decoded, lins):
-                trio = []
-                for t in (mel[0], lin, attn):
-                    trio.append(flat[o:o + t.numel()].reshape(tuple(t.shape)))
-                    o += t.numel()
-                out.append((trio[0], trio[1].T, trio[2]))
-            return out
-        out = []
-        for mel, attn in decoded:
-            linear = F.linear(self._cbhg(mel, 'postnet', self._post_k), self.p['post_proj.weight']).transpose(1, 2)[0]
-            out.append((mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()))
-        return out
+
+        def form_groups(short):                                                    # neighbours in the order of step counts: they end together
+            steps = [(ms[i].size(1) + self.r - 1) // self.r for i in short]
+            return [[short[j] for j in group] for group in self._gta_groups(steps, int(max_batch))]
+
+        def decode(encs, launch):
+            g = [([encs[i] for i in group], [ms[i] for i in group]) for group in launch]
+            return [self._decode_forced_kernel(*g[0])] if len(g) == 1 else self._decode_forced_launch(g)
+        # (more than 256 ids: the eager loop on the device)
+        return self._batch_frame(list_of_ids, front, groups, form_groups, decode, lambda i, e: self._decode_forced_eager(e[0], e[1], ms[i]))
 
     @torch.no_grad()
     def generate(self, ids, steps=2000, kernel=False, kernel_variant=0, cbhg_kernel=False):
@@ -839,23 +752,18 @@ class TacotronInference:
         (csrc/wrnn_cbhg.hip) instead of the torch ops; a state dict whose dims `wrnn_taco_front_create` refuses stays on the torch ops.
         `self.last_front_path` says which: 'hip' or 'torch'."""
         dev = self.device
-        if cbhg_kernel and dev.type != 'cuda':
-            from . import _lib
-            raise _lib.WrnnError('the encoder / post-net kernels need a HIP device (no CPU fallback)')
-        self._bigru_kernel = bool(kernel) and dev.type == 'cuda'                   # the CBHGs' GRUs as persistent kernels too
-        front = bool(cbhg_kernel) and self._front_handle() is not None
-        self.last_front_path = 'hip' if front else 'torch'
+        front = self._front_path(kernel, cbhg_kernel)
         seq, seq_proj = self.encode_kernel(ids)[:2] if front else self.encode(ids)
-        n = seq.size(1)
-        z = lambda *s: torch.zeros(*s, device=dev)
-        st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
-                  c2=z(1, self.lstm_dims), context=z(1, self.decoder_dims), cumulative=z(1, n), attention=z(1, n))
-        prenet_in = z(1, self.n_mels)                                              # the <GO> frame
-        frames, scores_all = [], []
         if kernel:
-            mel, scores_all = self._decode_kernel(seq, seq_proj, steps, kernel_variant)
+            mel, attn = self._decode_kernel(seq, seq_proj, steps, kernel_variant)
             frames = [mel]
         else:
+            n = seq.size(1)
+            z = lambda *s: torch.zeros(*s, device=dev)
+            st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
+                      c2=z(1, self.lstm_dims), context=z(1, self.decoder_dims), cumulative=z(1, n), attention=z(1, n))
+            prenet_in = z(1, self.n_mels)                                          # the <GO> frame
+            frames, scores_all = [], []
             for t in range(0, steps, self.r):
                 m_, s_ = self._decoder_step(seq, seq_proj, prenet_in, st)
                 frames.append(m_)
@@ -863,13 +771,9 @@ class TacotronInference:
                 prenet_in = m_[:, :, -1]
                 if (m_ < self.stop_threshold).all() and t > 10:
                     break
+            attn = torch.cat([s.unsqueeze(-1).transpose(1, 2) for s in scores_all], 1)[0]
         mel = torch.cat(frames, dim=2)
-        if front:
-            linear = self.postnet_kernel(mel)[0].transpose(0, 1)
-        else:
-            post = self._cbhg(mel, 'postnet', self._post_k)
-            linear = F.linear(post, self.p['post_proj.weight']).transpose(1, 2)[0]
-        attn = scores_all if kernel else torch.cat([s.unsqueeze(-1).transpose(1, 2) for s in scores_all], 1)[0]
+        linear = self._postnet(mel, front)
         return mel[0].cpu().numpy(), linear.cpu().numpy(), attn.cpu().numpy()
 
 
