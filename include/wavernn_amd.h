@@ -478,6 +478,40 @@ int wrnn_post_unfold(const float *segments, int32_t T, int32_t n_utt, const int3
 const char *wrnn_post_last_error(void);
 
 /*
+ * The same stage for a RANGE OF STEPS of many ragged, unfolded utterances (appended to ABI v9: the symbols tell whether a library has them): what a
+ * caller enqueues behind every step slice of a continued loop call (wrnn_options.t_begin / t_end) to hand finished audio on while the loop goes on --
+ * `batch.generate_unbatched`, `WaveRNN.generate_stream`; INTEGRATION.md "Streaming unbatched audio".  Utterance u is row row[u] of `segments` (NULL:
+ * row u), one UNFOLDED segment of wave_len[u] samples.  Element (u, t - t0) of the outputs, t in [t0, t1):
+ *   t <  wave_len[u]             lut[class of the sample] (`decode_mu_law`) or (double)sample, as wrnn_post_unfold with batched = 0;
+ *   t >= wave_len[u] - tail_len  ... times tail[t - (wave_len[u] - tail_len)]: ONE double multiply, in the order of wrnn_post_unfold (:256-258);
+ *   t >= wave_len[u]             0.0.
+ * out64 holds that double, out32 the double rounded to the nearest float32 (what `save_wav`'s `.astype(np.float32)` makes of it).  So the chunks of
+ * [0, T) in step order, each cut at wave_len[u], ARE the waveform wrnn_post_unfold writes, bit for bit, for any t0 / t1 / T (no alignment asked).
+ * wrnn_post_chunk: DEVICE pointers; one launch, asynchronous on `stream`; no allocation, no synchronisation, no workspace.  wrnn_post_chunk_host:
+ * the same struct with HOST pointers (`stream` ignored), computed by the calling thread, the HIP runtime is not touched; the two give the same bits
+ * (there is no transcendental in either).  WRNN_ERR_ARG with a message through wrnn_post_last_error(), before anything is launched: a struct size
+ * mismatch, a NULL segments / wave_len / tail, both outputs NULL, n_utt < 1, a range that is not 0 <= t0 < t1 <= T, tail_len < 0, lut with
+ * n_classes < 2; the host form also: a wave_len[u] < tail_len (the reference raises there, :258) or a negative row[u] -- the device form cannot read
+ * them, its caller checks.  wave_len[u] > T is allowed: steps past T are never asked for.
+ */
+typedef struct wrnn_post_chunk_call {
+    uint32_t struct_bytes;
+    int32_t n_utt, T;            /* utterances; row length of `segments` */
+    int32_t t0, t1;              /* steps [t0, t1), 0 <= t0 < t1 <= T */
+    int32_t n_classes, tail_len; /* n_classes is read only with lut */
+    const float  *segments;      /* [rows][T]: the loop's `out` */
+    const int32_t *row;          /* [n_utt] row of utterance u, or NULL (row u) */
+    const int32_t *wave_len;     /* [n_utt] */
+    const double *lut;           /* mu-law expansion table or NULL, as wrnn_post_unfold */
+    const double *tail;          /* [tail_len] = linspace(1, 0, 20*hop) */
+    double *out64;               /* [n_utt][t1-t0] or NULL */
+    float  *out32;               /* [n_utt][t1-t0] or NULL; at least one of the two */
+    void *stream;
+} wrnn_post_chunk_call;
+int wrnn_post_chunk(const wrnn_post_chunk_call *c);
+int wrnn_post_chunk_host(const wrnn_post_chunk_call *c);
+
+/*
  * BASELINE config 3's caller, the Tacotron side (ids -> mel -> linear), in three steps: wrnn_taco_encode (embedding, encoder pre-net, encoder CBHG,
  * `encoder_proj`: reference models/tacotron.py:24-39, :403-404; once per sentence), wrnn_taco_decode (the decoder loop as one persistent
  * kernel, SURVEY.md section 8 row f3: it replaces the per-frame loop of `Tacotron.generate()`, :396-414, around `Decoder.forward`, :218-279;

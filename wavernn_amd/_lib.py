@@ -28,7 +28,7 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_workspace_bytes_many',
            'wrnn_pre_upsample_many', 'wrnn_pre_debug_host_handle', 'wrnn_pre_last_error',
-           'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
+           'wrnn_post_unfold', 'wrnn_post_last_error', 'wrnn_post_chunk', 'wrnn_post_chunk_host', 'wrnn_taco_workspace_bytes', 'wrnn_taco_decode', 'wrnn_taco_status',
            'wrnn_taco_last_error', 'wrnn_bigru', 'wrnn_taco_front_create', 'wrnn_taco_front_destroy', 'wrnn_taco_front_workspace_bytes',
            'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch',
            'wrnn_bigru_many', 'wrnn_taco_front_workspace_bytes_many', 'wrnn_taco_encode_many', 'wrnn_taco_postnet_many',
@@ -179,6 +179,17 @@ class NllCall(ctypes.Structure):
         self.struct_bytes = ctypes.sizeof(NllCall)
 
 
+class PostChunkCall(ctypes.Structure):
+    """wrnn_post_chunk_call: the post-loop stage of a step range (wrnn_post_chunk: device pointers; wrnn_post_chunk_host: host pointers)."""
+    _fields_ = [('struct_bytes', ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ('n_utt', 'T', 't0', 't1', 'n_classes', 'tail_len')] + \
+               [(n, ctypes.c_void_p) for n in ('segments', 'row', 'wave_len', 'lut', 'tail', 'out64', 'out32', 'stream')]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_bytes = ctypes.sizeof(PostChunkCall)
+
+
 #: wrnn_options.progress: void (*)(int32 steps_done, int32 T, int32 n_segments, void *user)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p)
 
@@ -282,6 +293,8 @@ def lib():
                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     L.wrnn_post_last_error.restype = ctypes.c_char_p
+    L.wrnn_post_chunk.argtypes = [ctypes.POINTER(PostChunkCall)]
+    L.wrnn_post_chunk_host.argtypes = [ctypes.POINTER(PostChunkCall)]
     L.wrnn_taco_workspace_bytes.restype = ctypes.c_size_t
     L.wrnn_taco_decode.argtypes = [ctypes.c_int, ctypes.POINTER(TacoWeights), ctypes.POINTER(TacoCall)]
     L.wrnn_taco_status.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32 * 4), ctypes.c_void_p]
@@ -342,6 +355,31 @@ def nll_host(mode, logits, target, seg_len=None, per_step=True):
                 seg_len=None if lens is None else lens.ctypes.data, nll=None if nll is None else nll.ctypes.data, sum=total.ctypes.data)
     check(lib().wrnn_nll_host(ctypes.byref(c)), 'wrnn_nll_host')
     return nll, total
+
+
+def post_chunk_host(segments, wave_len, t0, t1, tail, lut=None, row=None, want64=True, want32=False):
+    """`wrnn_post_chunk_host`: steps [t0, t1) of the post-loop stage of unfolded utterances, by the calling thread.  segments (rows, T) float32,
+    wave_len (n,) int32, tail (tail_len,) float64, lut (n_classes,) float64 or None, row (n,) int32 or None -- host arrays.  Returns
+    (out64 (n, t1 - t0) float64 or None, out32 float32 or None).  No HIP device is needed."""
+    import numpy as np
+    segments = np.ascontiguousarray(segments, np.float32)
+    wave_len, tail = np.ascontiguousarray(wave_len, np.int32), np.ascontiguousarray(tail, np.float64)
+    lut = None if lut is None else np.ascontiguousarray(lut, np.float64)
+    row = None if row is None else np.ascontiguousarray(row, np.int32)
+    n = wave_len.shape[0]
+    if segments.ndim != 2 or (row is not None and (row.shape != (n,) or (n and int(row.max()) >= segments.shape[0]))) or (row is None and n > segments.shape[0]):
+        raise ValueError('segments: (rows, T); one row per utterance')
+    w = max(0, int(t1) - int(t0))
+    out64 = np.empty((n, w), np.float64) if want64 else None
+    out32 = np.empty((n, w), np.float32) if want32 else None
+    c = PostChunkCall(n_utt=n, T=segments.shape[1], t0=int(t0), t1=int(t1), n_classes=0 if lut is None else lut.shape[0], tail_len=tail.shape[0],
+                      segments=segments.ctypes.data, row=None if row is None else row.ctypes.data, wave_len=wave_len.ctypes.data,
+                      lut=None if lut is None else lut.ctypes.data, tail=tail.ctypes.data, out64=None if out64 is None else out64.ctypes.data,
+                      out32=None if out32 is None else out32.ctypes.data)
+    rc = lib().wrnn_post_chunk_host(ctypes.byref(c))
+    if rc != WRNN_OK:
+        raise WrnnError(f'wrnn_post_chunk_host failed (rc={rc}): {lib().wrnn_post_last_error().decode()}')
+    return out64, out32
 
 
 def noise_fill_host(mode, n_segments, n_classes, t_begin, t_end, seed, seg_id=None):

@@ -482,3 +482,293 @@ def generate_corpus(model, mels: Sequence, target: int, overlap: int, mu_law: bo
         if timings is not None:
             timings['gather_wait_ms'] = timings.get('gather_wait_ms', 0.0) + (time.perf_counter() - t_w) * 1e3
     return outs
+
+
+# ---- unbatched generation of a LIST of utterances: one unfolded segment each, one segment table per group, optionally streamed in step slices ----
+def _unbatched_plan(frames, hop) -> Plan:
+    """The one-fold-per-utterance plan of a group (what `pack_noise` reads): utterance k is segment k, frames[k] * hop conditioning positions from
+    o_k on, T = the longest."""
+    lengths = [int(f) * hop for f in frames]
+    n, T = len(lengths), max(lengths)
+    off = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    if int(off[-1]) + lengths[-1] + T >= 2 ** 31:
+        raise ValueError('concatenated conditioning exceeds int32 positions; lower max_utterances')
+    idx = np.arange(n, dtype=np.int64)
+    return Plan(T, 0, T, T, lengths, off, np.ones(n, np.int64), idx, off.astype(np.int32), (off + np.asarray(lengths)).astype(np.int32), idx.astype(np.int32))
+
+
+def unbatched_groups(frames: Sequence[int], max_utterances: int):
+    """Utterance indices sorted by frame count -- stable, longest first -- and cut into groups of at most `max_utterances`."""
+    order = sorted(range(len(frames)), key=lambda u: -int(frames[u]))
+    return [order[i:i + max_utterances] for i in range(0, len(order), max_utterances)]
+
+
+def _cut(t0, t1, bound):
+    """[t0, t1) in equal pieces of at most `bound` steps."""
+    pieces = -(-(t1 - t0) // max(1, bound))
+    size = -(-(t1 - t0) // pieces)
+    return [(a, min(t1, a + size)) for a in range(t0, t1, size)]
+
+
+_WARNED_WHOLE = 'wavernn_amd: chunk_steps asks for step slices, but {} does not continue a call (engine.RESUMABLE_KERNELS): the call runs whole and ' \
+                'every utterance is delivered as one chunk at the end'
+
+
+def unbatched_chunks(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequence[int]] = None, noise_source='library', chunk_steps: Optional[int] = None,
+                     max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None, global_rng=False):
+    """The core of `generate_unbatched` and `WaveRNN.generate_stream`, as a generator of (u, start, samples): utterance u's finished samples
+    [start, start + len(samples)), in step order and, within a step slice, in the group's order; `samples` is an array of its own.  While the
+    generator is suspended the device goes on with the slice queued behind the one just delivered.  global_rng (one utterance, 'cpu' noise): draw
+    from torch's global generator as `WaveRNN.generate` does, instead of a private generator seeded with seeds[u]."""
+    from .rng import draw_steps, burn_ctor_draws
+    from . import _lib
+    from . import post as _post
+    from .engine import RESUMABLE_KERNELS
+    t_call = time.perf_counter()
+    if noise_source not in ('cpu', 'device', 'library'):
+        raise ValueError(f'unknown noise source {noise_source!r}')
+    if noise_source in ('cpu', 'library') and seeds is None and not (global_rng and noise_source == 'cpu'):
+        raise ValueError(f"noise_source={noise_source!r} needs `seeds` (one per utterance); pass noise_source='device' to draw from the device generator instead")
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype: np.float64 or np.float32')
+    if chunk_steps is not None and int(chunk_steps) < 1 or int(max_utterances) < 1:
+        raise ValueError('chunk_steps and max_utterances are positive')
+    mels = [torch.as_tensor(m) for m in mels]
+    mels = [m.unsqueeze(0) if m.dim() == 2 else m for m in mels]
+    if not mels or (seeds is not None and len(seeds) != len(mels)) or (global_rng and len(mels) != 1):
+        raise ValueError('one seed per utterance, at least one utterance')
+    device = next(model.parameters()).device
+    if loop_fn is None:
+        model._require_hip_device(device)
+    mode, hop, C = model.mode, model.hop_length, model.n_classes
+    mu_law = bool(mu_law) if mode == 'RAW' else False
+    frames = [int(m.size(-1)) for m in mels]
+    tail_len = 20 * hop
+    for f in frames:               # the reference's tail fade raises here (:258), after its loop; this path before anything is launched
+        if (f - 1) * hop < tail_len:
+            raise ValueError(f'operands could not be broadcast together with shapes ({(f - 1) * hop},) ({tail_len},)')
+    want32 = dtype == np.dtype(np.float32)
+    was_training = model.training
+    model.eval()
+    loop_ms, n_slices, first_seen, warned = 0.0, 0, False, False
+    slab_tuning = 8192 if getattr(model, 'slab_prep_split', False) else 0
+    noise_bytes = int(getattr(model, 'noise_chunk_bytes', 2 << 30))
+    try:
+        with torch.no_grad():
+            for utts in unbatched_groups(frames, int(max_utterances)):
+                fr = [frames[u] for u in utts]
+                plan = _unbatched_plan(fr, hop)
+                n, T = len(utts), plan.T
+                wave_len = np.array([(f - 1) * hop for f in fr], dtype=np.int32)
+                seg_pos, seg_lim = plan.seg_pos, plan.seg_lim
+                # the materialised conditioning of the group's utterances, concatenated (each starts on a frame boundary): score_corpus' pre-loop path
+                if loop_fn is None and getattr(model, 'pre_algo', 'torch') == 'native':
+                    pre = model._pre_engine()
+                    mels_up = torch.empty(sum(fr) * hop, mels[utts[0]].size(1), dtype=torch.float32, device=device)
+                    aux = torch.empty(sum(fr), 4 * model.aux_dims, dtype=torch.float32, device=device)
+                    jobs = [(mels[u], mels_up[int(p):int(p) + f * hop], aux[int(p) // hop:int(p) // hop + f]) for u, p, f in zip(utts, seg_pos, fr)]
+                    pre.upsample_many(jobs, rows=False, streams=int(getattr(model, 'pre_streams', 8)), batched=bool(getattr(model, 'pre_batched', True)))
+                else:
+                    ups, auxs = zip(*[model.conditioning(mels[u])[:2] for u in utts])
+                    mels_up, aux = torch.cat(ups).contiguous(), torch.cat(auxs).contiguous()
+
+                gens = {}
+
+                def seed_streams():
+                    """the reference's per-utterance CPU streams: one private generator per utterance, the GRUCell constructor draws burnt once"""
+                    if noise_source != 'cpu':
+                        return
+                    for u in utts:
+                        gens[u] = None if global_rng else torch.Generator(device='cpu').manual_seed(int(seeds[u]))
+                        burn_ctor_draws(model.rnn_dims, model.aux_dims, 'cpu', gens[u])
+                lib_ids = np.concatenate([library_seg_ids(seeds[u], 1) for u in utts]) if noise_source == 'library' else None
+                lib_kw = dict(noise_seed=int(getattr(model, 'noise_key', 0)), noise_seg_id=lib_ids) if lib_ids is not None else {}
+
+                def draw(s0, s1):
+                    """noise rows of loop steps [s0, s1) of the group's segments, on the device (None: the loop draws them)"""
+                    if noise_source == 'library':
+                        if loop_fn is None:
+                            return None
+                        return torch.from_numpy(_lib.noise_fill_host(mode, n, C, s0, s1, lib_kw['noise_seed'], lib_ids)).to(device)
+                    if noise_source != 'cpu':
+                        return draw_steps(mode, n, s1 - s0, C, device, 'device')
+                    per_utt = [draw_steps(mode, 1, s1 - s0, C, 'cpu', 'cpu', generator=gens[u]) for u in utts]
+                    return pack_noise(mode, plan, per_utt, 0, n, steps=s1 - s0).to(device)
+
+                def deliver(arr, t0, t1):
+                    """chunks of steps [t0, t1) from arr [n][t1 - t0], in the group's order; copies, so that the staging buffer can be reused"""
+                    nonlocal first_seen
+                    for k, u in enumerate(utts):
+                        if t0 < int(wave_len[k]):
+                            if not first_seen and timings is not None:
+                                timings['first_chunk_ms'] = (time.perf_counter() - t_call) * 1e3
+                            first_seen = True
+                            yield u, t0, arr[k, :min(t1, int(wave_len[k])) - t0].copy()
+
+                if loop_fn is not None:         # the stand-in hook: the whole call at once, the chunks through wrnn_post_chunk_host
+                    seed_streams()
+                    segs = np.ascontiguousarray(torch.as_tensor(loop_fn(mels_up, aux, seg_pos, seg_lim, T, draw(0, T), hop)).cpu().numpy(), dtype=np.float32)
+                    tail, lut = _post.chunk_host_tables(hop, C, mu_law)
+                    k_steps = T if chunk_steps is None else min(int(chunk_steps), T)
+                    for t0, t1 in [(a, min(T, a + k_steps)) for a in range(0, T, k_steps)]:
+                        o64, o32 = _lib.post_chunk_host(segs, wave_len, t0, t1, tail, lut, want64=not want32, want32=want32)
+                        n_slices += 1
+                        yield from deliver(o32 if want32 else o64, t0, t1)
+                    continue
+
+                eng = model._loop_engine()
+                kernel = eng.plan(n, T, algo=model.loop_algo)['kernel']
+                resumable = kernel in RESUMABLE_KERNELS
+                groups = model.loop_sparse_groups(eng, n, T) if hasattr(model, 'loop_sparse_groups') else 0
+                sliced = chunk_steps is not None and resumable
+                if chunk_steps is not None and not resumable and not warned:
+                    import warnings
+                    warnings.warn(_WARNED_WHOLE.format(kernel))
+                    warned = True
+                # the noise bound of generate() / generate_corpus: at most `model.noise_chunk_bytes` of it resident, on the kernels that continue a call
+                bound = T
+                if noise_source != 'library' and resumable:
+                    bound = max(1, min(T, noise_bytes // (n * (11 if mode == 'MOL' else C) * 4)))
+                out = torch.empty(n, T, dtype=torch.float32, device=device)
+                run_kw = dict(algo=model.loop_algo, check=False, out=out, sparse_groups=groups, tuning=slab_tuning, **lib_kw)
+                rng_state = torch.get_rng_state() if (global_rng and noise_source == 'cpu') else None
+
+                def run(s0, s1):
+                    eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(s0, s1), hop, t_range=None if (s0 == 0 and s1 == T) else (s0, s1), **run_kw)
+
+                seed_streams()
+                if not sliced:
+                    try:
+                        for s0, s1 in _cut(0, T, bound):
+                            run(s0, s1)
+                    except _lib.ResidencyError as e:
+                        import warnings
+                        warnings.warn(f'wavernn_amd: {e}; redoing the group unsliced on the next kernel')
+                        if rng_state is not None:
+                            torch.set_rng_state(rng_state)
+                        seed_streams()
+                        run(0, T)
+                else:
+                    # ---- streamed: behind every step slice one wrnn_post_chunk launch on the SAME stream (the persistent loop kernel holds every CU: a
+                    #      kernel on another stream would only wait behind it), an event, and the chunk's copy into one of two page-locked buffers on ONE
+                    #      side stream (the copy engine).  The next slice is queued BEFORE the host waits for that copy.
+                    k_steps = min(int(chunk_steps), T)
+                    main = torch.cuda.current_stream(device)
+                    side = torch.cuda.Stream(device)
+                    t_dtype = torch.float32 if want32 else torch.float64
+                    dev_buf = [torch.empty(n * k_steps, dtype=t_dtype, device=device) for _ in range(2)]
+                    for d in dev_buf:
+                        d.record_stream(side)                      # (read by the copies on the side stream: a generator closed early frees them safely)
+                    pin_buf = [torch.empty(n * k_steps, dtype=t_dtype, pin_memory=True) for _ in range(2)]
+                    post_done = [torch.cuda.Event() for _ in range(2)]
+                    copy_done = [torch.cuda.Event() for _ in range(2)]
+                    wl_dev = torch.from_numpy(wave_len).to(device)
+                    pending, fell_back = None, False
+                    slices = [(a, min(T, a + k_steps)) for a in range(0, T, k_steps)]
+                    for i, (t0, t1) in enumerate(slices):
+                        b = i % 2
+                        try:
+                            for s0, s1 in _cut(t0, t1, bound):
+                                run(s0, s1)
+                        except _lib.ResidencyError as e:
+                            if i:
+                                raise
+                            # the persistent grid was refused on the first slice (a continuation cannot change kernels): the group unsliced on the
+                            # next kernel, from the start of every utterance's noise stream -- what generate() and generate_corpus do
+                            import warnings
+                            warnings.warn(f'wavernn_amd: {e}; redoing the group unsliced on the next kernel')
+                            if rng_state is not None:
+                                torch.set_rng_state(rng_state)
+                            seed_streams()
+                            run(0, T)
+                            fell_back = True
+                            break
+                        if i >= 2:
+                            main.wait_event(copy_done[b])          # the copy of slice i - 2 has left this device buffer
+                        w = t1 - t0
+                        d = dev_buf[b][:n * w]
+                        _post.chunk_on_device(out, wl_dev, t0, t1, hop, C, mu_law, out64=None if want32 else d, out32=d if want32 else None,
+                                              min_wave_len=int(wave_len.min()))
+                        post_done[b].record(main)
+                        side.wait_event(post_done[b])
+                        with torch.cuda.stream(side):
+                            pin_buf[b][:n * w].copy_(d, non_blocking=True)
+                        copy_done[b].record(side)
+                        n_slices += 1
+                        if pending is not None:                    # (slice i is queued: now the host may wait for slice i - 1)
+                            pb, p0, p1 = pending
+                            copy_done[pb].synchronize()
+                            yield from deliver(pin_buf[pb][:n * (p1 - p0)].numpy().reshape(n, p1 - p0), p0, p1)
+                        pending = (b, t0, t1)
+                    if not fell_back:
+                        pb, p0, p1 = pending
+                        copy_done[pb].synchronize()
+                        if check:
+                            eng.status()                           # after the last slice: no wrnn_status between slices (it synchronises)
+                        yield from deliver(pin_buf[pb][:n * (p1 - p0)].numpy().reshape(n, p1 - p0), p0, p1)
+                        side.synchronize()
+                        model.last_loop_ms, model.last_loop_kernel = eng.last_loop_ms(), eng.last_loop_kernel()
+                        loop_ms += model.last_loop_ms
+                        continue
+                # ---- the loop ran whole: ONE unfold launch finishes every utterance of the group; each is delivered as one chunk
+                from .post import unfold_on_device
+                wav, sl = unfold_on_device(out, list(range(n)), [1] * n, [int(w) for w in wave_len], 0, hop, C, mu_law, False)
+                host = torch.empty(wav.shape, dtype=wav.dtype, pin_memory=True)
+                host.copy_(wav, non_blocking=True)
+                if check:
+                    eng.status()
+                torch.cuda.current_stream(device).synchronize()
+                model.last_loop_ms, model.last_loop_kernel = eng.last_loop_ms(), eng.last_loop_kernel()
+                loop_ms += model.last_loop_ms
+                host = host.numpy()
+                n_slices += 1
+                for k, u in enumerate(utts):
+                    if not first_seen and timings is not None:
+                        timings['first_chunk_ms'] = (time.perf_counter() - t_call) * 1e3
+                    first_seen = True
+                    yield u, 0, host[sl[k][0]:sl[k][1]].astype(dtype)       # (float32: the double rounded to nearest, as wrnn_post_chunk's out32)
+    finally:
+        if timings is not None:
+            timings['loop_ms'], timings['slices'] = loop_ms, n_slices
+        if was_training:
+            model.train()
+
+
+def generate_unbatched(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequence[int]] = None, noise_source='library', chunk_steps: Optional[int] = None,
+                       on_chunk=None, max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None):
+    """Generate every utterance of `mels` (each (1, feat, N_u) or (feat, N_u)) UNBATCHED -- no folds, no cross-fade seams: the quality mode of
+    `generate(batched=False)` -- as the unfolded segments of one loop call per group, and optionally hand the audio on in step slices while the loop
+    goes on.  Returns the list of waveforms (`dtype`, (N_u - 1) * hop samples each) in the caller's order.
+
+    Groups: the utterances sorted by frame count (stable, longest first) and cut into groups of at most `max_utterances`; a group is ONE segment
+    table over the concatenated, materialised conditioning (seg_pos = o_u, seg_lim = o_u + N_u * hop, T = the group's longest N_u * hop), so a list
+    costs its longest utterance, not the sum.  The default of 64 is where the dense latency kernel's step time is still flat (wrnn_chain_kernel
+    carries 4 clusters x 16 segments at the step time of one); a pruned model (wrnn_sparse_kernel) may be given 256.
+
+    Noise: 'library' (default): utterance u under the stream id `library_seg_ids(seeds[u], 1)` and the key `model.noise_key` -- its audio equals
+    `generate(mel_u, ..., batched=False, ...)` alone with `model.noise_source = 'library'` and `model.noise_seed = seeds[u]`.  'cpu': one private
+    generator per utterance seeded seeds[u], the constructor draws burnt once, drawn in step slices bounded by `model.noise_chunk_bytes` -- the
+    reference's unbatched `generate` after `torch.manual_seed(seeds[u])`.  'device': the device generator (`seeds` unused).
+
+    chunk_steps=None: the loop runs whole (or in noise slices) and `wrnn_post_unfold` finishes all utterances of a group in one launch.
+    chunk_steps=k, on a kernel that continues a call (`engine.RESUMABLE_KERNELS`): the loop runs in slices of k steps; behind every slice one
+    `wrnn_post_chunk` launch on the same stream and the chunk's copy into one of two page-locked buffers on a side stream, the next slice queued
+    before the host waits for that copy.  Any other kernel runs the call whole and delivers each utterance as one chunk at the end (one warning).
+
+    on_chunk(u, start, samples), on the calling thread, in step order and within a slice in the group's order, for every utterance with
+    start < wave_len_u: `samples` (length min(t1, wave_len_u) - start) is a copy the callee may keep.  The returned waveforms are assembled from
+    the same chunks.  check=True: `eng.status()` after the last slice of a group (never between slices: it synchronises); raises if a kernel gave up.
+    A mel of fewer than 21 frames raises the reference's ValueError (wave_len < 20 * hop, :258) before anything is launched.
+
+    loop_fn: the stand-in hook of `generate_corpus`, same signature; the chunks then go through `wrnn_post_chunk_host`, so the whole host path runs
+    without a GPU.  timings: optional dict, receives loop_ms (summed over the groups), first_chunk_ms (wall time from the call to the first chunk)
+    and slices (post-loop launches)."""
+    parts = [[] for _ in mels]
+    for u, start, samples in unbatched_chunks(model, mels, mu_law, seeds=seeds, noise_source=noise_source, chunk_steps=chunk_steps,
+                                              max_utterances=max_utterances, dtype=dtype, loop_fn=loop_fn, check=check, timings=timings):
+        assert start == sum(len(p) for p in parts[u])
+        if on_chunk is not None:
+            on_chunk(u, start, samples)
+        parts[u].append(samples)
+    return [p[0] if len(p) == 1 else np.concatenate(p) for p in parts]

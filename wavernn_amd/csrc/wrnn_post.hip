@@ -29,7 +29,8 @@ struct PostArgs {
     int n_utt, T, overlap, tail_len, n_classes, batched;
 };
 
-__device__ __forceinline__ double post_value(const PostArgs &a, int row, int o)
+// (__host__ too: wrnn_post_chunk_host runs the same expression on the calling thread -- rintf, an int clamp, a table read or a widening cast)
+__host__ __device__ __forceinline__ double post_value(const PostArgs &a, int row, int o)
 {
     const float y = a.seg[(size_t)row * a.T + o];
     double v;
@@ -71,6 +72,54 @@ __global__ __launch_bounds__(256) void wrnn_post_kernel(const PostArgs a)
     }
 }
 
+// ---- the same stage for a RANGE OF STEPS of many ragged, unfolded utterances (wrnn_post_chunk): element (u, t) of steps [t0, t1) is
+// post_value of row[u] at step t, times the tail ramp from wave_len[u] - tail_len on, 0.0 from wave_len[u] on -- one double multiply, in the
+// order of wrnn_post_kernel.  Element-wise and coalesced along t with plain dword / qword accesses: the row base row * T + t0 has no alignment.
+struct ChunkArgs {
+    const float *seg;        // [rows][T] loop output
+    const int *row;          // [n_utt] or nullptr (row u)
+    const int *wave_len;     // [n_utt]
+    const double *lut;       // [n_classes] or nullptr
+    const double *tail;      // [tail_len]
+    double *out64;           // [n_utt][t1 - t0] or nullptr
+    float *out32;            // [n_utt][t1 - t0] or nullptr
+    int n_utt, T, t0, t1, n_classes, tail_len;
+};
+
+__host__ __device__ __forceinline__ PostArgs chunk_view(const ChunkArgs &c)
+{
+    PostArgs a;
+    a.seg = c.seg; a.first = nullptr; a.folds = nullptr; a.out_off = nullptr; a.lut = c.lut; a.fade_in = nullptr; a.fade_out = nullptr;
+    a.tail = c.tail; a.out = nullptr; a.n_utt = c.n_utt; a.T = c.T; a.overlap = 0; a.tail_len = c.tail_len; a.n_classes = c.n_classes; a.batched = 0;
+    return a;
+}
+
+// element i of utterance u's chunk (step t0 + i); every index stays in its array for any wave_len: t < t1 <= T, 0 <= tl < tail_len
+__host__ __device__ __forceinline__ void chunk_element(const ChunkArgs &c, const PostArgs &a, int u, int row, int wave_len, int i)
+{
+    const int t = c.t0 + i;
+    double v = 0.0;
+    if (t < wave_len) {
+        v = post_value(a, row, t);
+        const int tl = t - (wave_len - c.tail_len);
+        if (tl >= 0) v *= c.tail[tl];                                              // :256-258
+    }
+    const size_t o = (size_t)u * (size_t)(c.t1 - c.t0) + (size_t)i;
+    if (c.out64) c.out64[o] = v;
+    if (c.out32) c.out32[o] = (float)v;                                            // round to nearest: save_wav's .astype(np.float32)
+}
+
+// grid.y = utterance, grid-stride over the chunk's steps
+__global__ __launch_bounds__(256) void wrnn_post_chunk_kernel(const ChunkArgs c)
+{
+    const int u = blockIdx.y;
+    const int n = c.t1 - c.t0;
+    const int wave_len = c.wave_len[u];
+    const int row = c.row ? c.row[u] : u;
+    const PostArgs a = chunk_view(c);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) chunk_element(c, a, u, row, wave_len, i);
+}
+
 }  // namespace wrnn
 
 using namespace wrnn;
@@ -98,5 +147,65 @@ extern "C" int wrnn_post_unfold(const float *segments, int32_t T, int32_t n_utt,
         snprintf(g_post_err, sizeof g_post_err, "launch failed: %s", hipGetErrorString(e));
         return WRNN_ERR_HIP;
     }
+    return WRNN_OK;
+}
+
+// what both forms of wrnn_post_chunk refuse before they read an array
+static int check_chunk(const wrnn_post_chunk_call *c)
+{
+    if (!c) { snprintf(g_post_err, sizeof g_post_err, "NULL wrnn_post_chunk_call"); return WRNN_ERR_ARG; }
+    if (c->struct_bytes != sizeof(wrnn_post_chunk_call)) {
+        snprintf(g_post_err, sizeof g_post_err, "wrnn_post_chunk_call.struct_bytes is %u, this library's struct has %zu bytes", c->struct_bytes,
+                 sizeof(wrnn_post_chunk_call));
+        return WRNN_ERR_ARG;
+    }
+    const char *what = !c->segments ? "NULL segments" : !c->wave_len ? "NULL wave_len" : !c->tail ? "NULL tail" :
+                       (!c->out64 && !c->out32) ? "out64 and out32 are both NULL" : (c->n_utt < 1 || c->T < 1) ? "n_utt < 1 or T < 1" :
+                       !(0 <= c->t0 && c->t0 < c->t1 && c->t1 <= c->T) ? "bad step range: 0 <= t0 < t1 <= T" : c->tail_len < 0 ? "tail_len < 0" :
+                       (c->lut && c->n_classes < 2) ? "lut with n_classes < 2" : nullptr;
+    if (what) {
+        snprintf(g_post_err, sizeof g_post_err, "wrnn_post_chunk: %s (n_utt=%d T=%d t0=%d t1=%d tail_len=%d n_classes=%d)", what, c->n_utt, c->T, c->t0,
+                 c->t1, c->tail_len, c->n_classes);
+        return WRNN_ERR_ARG;
+    }
+    return WRNN_OK;
+}
+
+static ChunkArgs chunk_args(const wrnn_post_chunk_call *c)
+{
+    ChunkArgs a;
+    a.seg = c->segments; a.row = c->row; a.wave_len = c->wave_len; a.lut = c->lut; a.tail = c->tail; a.out64 = c->out64; a.out32 = c->out32;
+    a.n_utt = c->n_utt; a.T = c->T; a.t0 = c->t0; a.t1 = c->t1; a.n_classes = c->n_classes; a.tail_len = c->tail_len;
+    return a;
+}
+
+extern "C" int wrnn_post_chunk(const wrnn_post_chunk_call *c)
+{
+    if (int rc = check_chunk(c)) return rc;
+    const ChunkArgs a = chunk_args(c);
+    const int n = a.t1 - a.t0;
+    const int bx = (n + 255) / 256 < 64 ? (n + 255) / 256 : 64;
+    hipLaunchKernelGGL(wrnn_post_chunk_kernel, dim3(bx, a.n_utt), dim3(256), 0, (hipStream_t)c->stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_post_err, sizeof g_post_err, "launch failed: %s", hipGetErrorString(e));
+        return WRNN_ERR_HIP;
+    }
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_post_chunk_host(const wrnn_post_chunk_call *c)
+{
+    if (int rc = check_chunk(c)) return rc;
+    const ChunkArgs a = chunk_args(c);
+    for (int u = 0; u < a.n_utt; ++u)            // (the device form cannot read these: its caller checks)
+        if (a.wave_len[u] < a.tail_len || (a.row && a.row[u] < 0)) {
+            snprintf(g_post_err, sizeof g_post_err, "wrnn_post_chunk_host: utterance %d: wave_len %d < tail_len %d, or a negative row", u, a.wave_len[u],
+                     a.tail_len);
+            return WRNN_ERR_ARG;
+        }
+    const PostArgs v = chunk_view(a);
+    for (int u = 0; u < a.n_utt; ++u)
+        for (int i = 0; i < a.t1 - a.t0; ++i) chunk_element(a, v, u, a.row ? a.row[u] : u, a.wave_len[u], i);
     return WRNN_OK;
 }

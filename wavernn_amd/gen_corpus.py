@@ -10,6 +10,10 @@ writes the WAVs of the utterances whose first segment it owned.  `--seed S` give
 `torch.manual_seed(S + u)` (equal to a per-utterance `generate()` call with that seed); without it noise is drawn on the
 device.  `--noise library --seed S`: the loop draws its noise itself, utterance u under seed S + u (equal to
 `gen_wavernn --noise library --seed S+u`, whatever the batch and the rank count; no noise crosses the host).
+
+`--unbatched [--chunk-steps K]`: the quality mode -- no folds, no cross-fade seams -- for the whole directory in one pass (`batch.generate_unbatched`:
+every utterance one unfolded segment, up to 64 per loop call); single process; files are named `..gen_NOT_BATCHED.wav` as gen_wavernn names them.
+With --chunk-steps the audio leaves the device in slices of K steps while the loop goes on.
 """
 import argparse
 import os
@@ -19,7 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import ALGOS
-from .batch import generate_corpus
+from .batch import generate_corpus, generate_unbatched
 from .dsp import save_wav
 from .model import WaveRNN
 from .synthetic import SHIPPED
@@ -59,9 +63,17 @@ def main(argv=None):
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
                          "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
                          "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones")
+    ap.add_argument('--unbatched', '-u', action='store_true', help='no folds: every utterance one unfolded segment, up to 64 per loop call (single process)')
+    ap.add_argument('--chunk-steps', type=int, default=None, help='--unbatched: finish and copy out the audio in slices of K loop steps while the loop goes on')
     a = ap.parse_args(argv)
     if a.noise in ('cpu', 'library') and a.seed is None:
         ap.error(f'--noise {a.noise} needs --seed')
+    if a.chunk_steps is not None and not a.unbatched:
+        ap.error('--chunk-steps needs --unbatched')
+    if a.chunk_steps is not None and a.chunk_steps < 1:
+        ap.error('--chunk-steps: at least one step')
+    if a.unbatched and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('gen_corpus --unbatched runs in a single process (an unbatched list is not sharded over ranks); start it without a launcher')
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -82,14 +94,18 @@ def main(argv=None):
     model.loop_algo = a.algo
     paths, mels = load_mels(a.mels)
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
-    outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group,
-                           noise_source=a.noise or ('cpu' if seeds is not None else 'device'), finish='own')
+    noise = a.noise or ('cpu' if seeds is not None else 'device')
+    if a.unbatched:
+        outs = generate_unbatched(model, [m.to(dev) for m in mels], True, seeds, noise_source=noise, chunk_steps=a.chunk_steps)
+    else:
+        outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group, noise_source=noise, finish='own')
     out_dir = Path(a.output)
     out_dir.mkdir(parents=True, exist_ok=True)
     n = 0
     for p, y in zip(paths, outs):
         if y is not None:
-            save_wav(y, out_dir / f'__{p.stem}__gen_batched_target{a.target}_overlap{a.overlap}.wav', model.sample_rate)
+            batch_str = 'gen_NOT_BATCHED' if a.unbatched else f'gen_batched_target{a.target}_overlap{a.overlap}'
+            save_wav(y, out_dir / f'__{p.stem}__{batch_str}.wav', model.sample_rate)
             n += y.shape[0]
     eng = model._loop_engine()
     print(f'rank {rank}/{world}: wrote {sum(y is not None for y in outs)} of {len(outs)} utterances, {n / model.sample_rate:.1f} s of audio; '

@@ -8,12 +8,13 @@ Flags follow the reference where they exist (--input_text/-i, --tts_weights, --b
 --sentences (default: none) is synthesised.  Text cleaning is the basic pipeline (lowercase, whitespace): number and
 abbreviation expansion need the reference's text front-end (out of scope).
 
-`--batch N` (with --batched): all sentences at once -- the Tacotron decoder loops in groups of N <= 8 sentences per persistent kernel
+`--batch N`: all sentences at once -- the Tacotron decoder loops in groups of N <= 8 sentences per persistent kernel
 (`TacotronInference.generate_batch`, csrc/wrnn_taco_batch.hip), then ONE vocoder pass over all of them (`generate_corpus`, noise drawn inside the
 library under the seeds --seed, --seed + 1, ...).  Same file names.  With --cbhg_kernel the encoder and the post-net of all sentences run side by
 side as well (`wrnn_taco_encode_many` / `wrnn_taco_postnet_many`, one call each per 64 sentences).  Without the flag the per-sentence path runs as
 before.  `--groups 2` (with --batch, a device of 256 CUs): two decoder groups of N sentences per launch, one on each half of the device
-(`wrnn_taco_decode_batch_groups`); the same audio."""
+(`wrnn_taco_decode_batch_groups`); the same audio.  `--batch N --unbatched`: the same Tacotron side, and the vocoder pass is
+`generate_unbatched` -- every sentence one unfolded segment of one loop call, no folds and no cross-fade seams, the same seeds."""
 import argparse
 import time
 from pathlib import Path
@@ -26,7 +27,7 @@ from .synthetic import SHIPPED
 from .tacotron import TacotronInference, tacotron_to_wavernn_mel, text_to_ids
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='TTS Generator (Tacotron -> WaveRNN) on MI355X')
     ap.add_argument('--input_text', '-i', type=str, help='[string] Type in something here and TTS will generate it!')
     ap.add_argument('--sentences', type=str, help='text file, one sentence per line (the reference reads sentences.txt)')
@@ -40,17 +41,20 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=2000, help='decoder step limit (Tacotron.generate default)')
     ap.add_argument('--output', default='.', help='output directory')
     ap.add_argument('--cbhg_kernel', action='store_true', help='run the encoder and the post-net as HIP kernels too (wrnn_taco_encode / wrnn_taco_postnet; with --batch their _many forms)')
-    ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (needs --batched)')
+    ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (--unbatched: unfolded, generate_unbatched)')
     ap.add_argument('--groups', type=int, default=1, choices=[1, 2], help='--batch: decoder groups per launch (2: a group on each half of a 256-CU device)')
     ap.add_argument('--seed', type=int, default=0, help='--batch: sentence i draws its sampling noise under seed + i')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
-    if a.batch is not None and not a.batched:
-        ap.error('--batch needs --batched (the one-pass vocoder folds every sentence)')
     if a.batch is not None and not 1 <= a.batch <= 8:
         ap.error('--batch: 1..8 sentences per decoder kernel')
     if a.groups != 1 and a.batch is None:
         ap.error('--groups needs --batch')
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     voc = WaveRNN(**SHIPPED, mode=a.mode).to('cuda')
@@ -68,14 +72,18 @@ def main(argv=None):
     tts_k = int(tts.p['step'].item()) // 1000 if 'step' in tts.p else 0
     names = [f'__input_{text[:10]}_{v_type}_{tts_k}k.wav' if a.input_text else f'{i}_{v_type}_{tts_k}k.wav' for i, text in enumerate(texts, 1)]
     if a.batch is not None:
-        from .batch import generate_corpus
+        from .batch import generate_corpus, generate_unbatched
         from .dsp import save_wav
         print(f'\n| Generating {len(texts)} sentences, {a.batch} per decoder kernel')
         t0 = time.perf_counter()
         outs = tts.generate_batch([text_to_ids(t) for t in texts], steps=a.steps, kernel=True, cbhg_kernel=a.cbhg_kernel, max_batch=a.batch, groups=a.groups)
         t1 = time.perf_counter()
         mels = [torch.tensor(tacotron_to_wavernn_mel(lin)).unsqueeze(0) for _, lin, _ in outs]          # the POSTNET output (:142)
-        wavs = generate_corpus(voc, mels, a.target, a.overlap, True, seeds=[a.seed + i for i in range(len(mels))], noise_source='library')
+        seeds = [a.seed + i for i in range(len(mels))]
+        if a.batched:
+            wavs = generate_corpus(voc, mels, a.target, a.overlap, True, seeds=seeds, noise_source='library')
+        else:
+            wavs = generate_unbatched(voc, mels, True, seeds=seeds, noise_source='library')
         t2 = time.perf_counter()
         for name, wav, (_, lin, _) in zip(names, wavs, outs):
             save_wav(np.asarray(wav), out_dir / name, voc.sample_rate)

@@ -4,7 +4,10 @@ librosa-free mel front-end of dsp.py).
 
 Same flags as the reference where they exist (--batched/-b, --unbatched/-u, --target/-t, --overlap/-o, --file/-f,
 --weights/-w); the hparams.py machinery is replaced by flags with the shipped defaults (hparams.py:20-60).  Mel
-input must be a (80, N) or (1, 80, N) float array in [0, 1] (gen_wavernn.py:50-55 raises ValueError otherwise)."""
+input must be a (80, N) or (1, 80, N) float array in [0, 1] (gen_wavernn.py:50-55 raises ValueError otherwise).
+
+`--unbatched --stream`: the same file through `WaveRNN.generate_stream` -- the audio leaves the device in chunks of --chunk-steps loop steps while the
+loop goes on; the time to the first chunk is printed."""
 import argparse
 from pathlib import Path
 
@@ -16,7 +19,7 @@ from .model import WaveRNN
 from .synthetic import SHIPPED
 
 
-def gen_from_file(model, load_path: Path, save_path: Path, batched, target, overlap, mu_law=True):
+def gen_from_file(model, load_path: Path, save_path: Path, batched, target, overlap, mu_law=True, stream_steps=None):
     """gen_wavernn.py:38-65 for a `.npy` mel."""
     suffix = load_path.suffix
     if suffix == '.wav':
@@ -37,6 +40,17 @@ def gen_from_file(model, load_path: Path, save_path: Path, batched, target, over
     mel = torch.tensor(mel).unsqueeze(0)
     batch_str = f'gen_batched_target{target}_overlap{overlap}' if batched else 'gen_NOT_BATCHED'
     save_str = save_path / f'__{load_path.stem}__{batch_str}.wav'
+    if stream_steps is not None:        # (unbatched: the chunks of generate_stream, concatenated, are what generate returns)
+        import time
+        from .dsp import save_wav
+        t0, chunks, first = time.perf_counter(), [], None
+        for c in model.generate_stream(mel, mu_law, chunk_steps=stream_steps):
+            first = first if first is not None else time.perf_counter() - t0
+            chunks.append(c)
+        out = np.concatenate(chunks)
+        print(f'first chunk ({len(chunks[0])} samples) after {first * 1e3:.1f} ms, {len(chunks)} chunks in {(time.perf_counter() - t0) * 1e3:.1f} ms')
+        save_wav(out, save_str, model.sample_rate)
+        return out, save_str
     out = model.generate(mel, save_str, batched, target, overlap, mu_law)
     return out, save_str
 
@@ -60,8 +74,14 @@ def main(argv=None):
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
                          "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
                          "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones")
+    ap.add_argument('--stream', action='store_true', help='--unbatched: hand the audio on in chunks while the loop goes on (WaveRNN.generate_stream); prints the time to the first chunk')
+    ap.add_argument('--chunk-steps', type=int, default=2200, help='--stream: loop steps per chunk')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
+    if a.stream and a.batched:
+        ap.error('--stream needs --unbatched (a folded utterance is finished by its cross-fade, not step by step)')
+    if a.chunk_steps < 1:
+        ap.error('--chunk-steps: at least one step')
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')
     model = WaveRNN(**SHIPPED, mode=a.mode).to('cuda')
@@ -74,7 +94,8 @@ def main(argv=None):
     if a.seed is not None:
         torch.manual_seed(a.seed)
         model.noise_seed = a.seed
-    out, path = gen_from_file(model, Path(a.file).expanduser().resolve(), Path(a.output), a.batched, a.target, a.overlap)
+    out, path = gen_from_file(model, Path(a.file).expanduser().resolve(), Path(a.output), a.batched, a.target, a.overlap,
+                              stream_steps=a.chunk_steps if a.stream else None)
     n = out.shape[0]
     print(f'{path}: {n} samples ({n / model.sample_rate:.2f} s), loop {model.last_loop_kernel} {model.last_loop_ms:.1f} ms '
           f'= {n / model.last_loop_ms:.1f} kHz')

@@ -5,6 +5,8 @@ utils/dsp.py:98-103) for any number of utterances in one launch.
 Bit-exact with the reference by construction: the transcendental parts (pow of `decode_mu_law`, sqrt / linspace of the
 fades) are evaluated here with the reference's numpy expressions and uploaded as float64 tables; the kernel only gathers,
 multiplies and adds doubles in the reference's order."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -88,3 +90,42 @@ def unfold_on_device(segments, first, folds, wave_lens, overlap, hop, n_classes,
     if rc != 0:
         raise _lib.WrnnError(f'wrnn_post_unfold failed (rc={rc}): {L.wrnn_post_last_error().decode()}')
     return t.out, [(int(off[u]), int(off[u + 1])) for u in range(n_utt)]
+
+
+def chunk_host_tables(hop, n_classes, mu_law):
+    """(tail, lut or None): the float64 host tables of `_lib.post_chunk_host` -- the reference's numpy expressions, what the device tables are copies of."""
+    idx = np.arange(n_classes, dtype=np.float32)
+    y32 = np.float32(2.0) * idx / np.float32(n_classes - 1) - np.float32(1.0)
+    return np.linspace(1, 0, 20 * hop), (_fold.decode_mu_law(y32.astype(np.float64), n_classes, False) if mu_law else None)
+
+
+def chunk_on_device(segments, wave_len, t0, t1, hop, n_classes, mu_law, out64=None, out32=None, row=None, min_wave_len=None):
+    """One `wrnn_post_chunk` launch on the current stream: steps [t0, t1) of the post-loop stage of unfolded utterances.  segments: float32 CUDA
+    (rows, T), the loop's `out`, of which only [t0, t1) need be finished; wave_len: int32 CUDA (n,); row: int32 CUDA (n,) or None (utterance u is
+    row u); out64 / out32: float64 / float32 CUDA buffers of at least n * (t1 - t0) elements, at least one of them -- written as [n][t1 - t0].
+    Nothing is allocated, nothing synchronises.  The kernel cannot refuse what it reads from the device: the caller vouches that every wave_len is
+    >= 20 * hop (`min_wave_len`, the smallest of them, is checked here when given: the reference's ValueError, :258) and every row < segments.shape[0]."""
+    dev = segments.device
+    if not (segments.is_cuda and segments.dtype == torch.float32 and segments.is_contiguous() and segments.dim() == 2):
+        raise ValueError('segments must be a contiguous float32 CUDA tensor (rows, T)')
+    n, w = int(wave_len.shape[0]), int(t1) - int(t0)
+    if not (wave_len.is_cuda and wave_len.dtype == torch.int32 and wave_len.is_contiguous()) or \
+            (row is not None and not (row.is_cuda and row.dtype == torch.int32 and row.is_contiguous() and row.shape == wave_len.shape)):
+        raise ValueError('wave_len / row must be contiguous int32 CUDA tensors of one entry per utterance')
+    if row is None and n > segments.shape[0]:
+        raise ValueError('more utterances than rows of segments')
+    if min_wave_len is not None and min_wave_len < 20 * hop:
+        raise ValueError(f'operands could not be broadcast together with shapes ({min_wave_len},) ({20 * hop},)')
+    for o, dt in ((out64, torch.float64), (out32, torch.float32)):
+        if o is not None and not (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() >= n * max(w, 0)):
+            raise ValueError('out64 / out32: contiguous CUDA buffers of n * (t1 - t0) float64 / float32 elements')
+    _, _, tail = _fade_tables(0, hop, dev)
+    lut = _mu_law_lut(n_classes, dev) if mu_law else None
+    c = _lib.PostChunkCall(n_utt=n, T=int(segments.shape[1]), t0=int(t0), t1=int(t1), n_classes=int(n_classes), tail_len=20 * hop,
+                           segments=segments.data_ptr(), row=None if row is None else row.data_ptr(), wave_len=wave_len.data_ptr(),
+                           lut=None if lut is None else lut.data_ptr(), tail=tail.data_ptr(), out64=None if out64 is None else out64.data_ptr(),
+                           out32=None if out32 is None else out32.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+    L = _lib.lib()
+    rc = L.wrnn_post_chunk(ctypes.byref(c))
+    if rc != 0:
+        raise _lib.WrnnError(f'wrnn_post_chunk failed (rc={rc}): {L.wrnn_post_last_error().decode()}')
