@@ -85,6 +85,22 @@ enum {
                                at one half it ran at 0.87 x.)  Without a view: WRNN_ERR_ARG naming the matrix and its surviving
                                fraction, or the dim -- WRNN_ALGO_TILE runs such a pack dense.  An output element is one accumulator chain over its block row's
                                surviving columns in ascending order */
+    WRNN_ALGO_TILE_BF16 = 13, /* WRNN_ALGO_TILE with the weights in BFLOAT16 (csrc/wrnn_tile_bf16.hip, wrnn_tile_bf16_kernel; on request only, `auto` never picks
+                               it).  NOT THE REFERENCE'S ARITHMETIC: the eight loop matrices (I, rnn1 / rnn2 weight_ih / weight_hh, fc1, fc2, fc3) are rounded
+                               once, when the pack is built, to bfloat16, round-to-nearest-even; biases, activations, the GRU state and every pointwise pass
+                               stay float32.  THE ARITHMETIC CONTRACT: where an activation x is multiplied it is split in registers into three bf16 pieces by
+                               truncation -- hi = x & 0xFFFF0000, mid = (x - hi) & 0xFFFF0000, lo = x - hi - mid; hi + mid + lo == x exactly -- and the three
+                               products run on v_mfma_f32_16x16x32_bf16 into ONE float32 accumulator per output element, k-steps of 32 ascending, hi / mid /
+                               lo inside a step (the r and z gates of a GRU: W_ih's k-steps, then W_hh's, in one chain): float32 sums of exact products on
+                               the ROUNDED weights, i.e. what WRNN_ALGO_TILE computes on a model whose eight matrices were rounded the same way
+                               (wavernn_amd.synthetic.bf16_round_state_dict), up to the summation order.  What the rounding costs a checkpoint, in bits per
+                               sample: score it with WRNN_ALGO_TILE_BF16 and with WRNN_ALGO_TILE (score_wavernn --algo).  Same dataflow, grid, workspace,
+                               options and refusals as WRNN_ALGO_TILE, and THE SAME LDS RULE (row counts rounded up to 4; rnn = fc = 512 and 576 at feat 80,
+                               aux 32 fit, 640 does not); RAW: <= 2048 classes.  wrnn_pack_create builds the bf16 view for every generic pack whose dims
+                               pass that rule (wrnn_pack_tile_bf16()) unless a weight is not finite or rounds to +-inf; without a view: WRNN_ERR_ARG.
+                               Measured against WRNN_ALGO_TILE on the same pack, T = 2000 (profiles/tile_bf16_ab.json): 1.76 - 1.81 x its throughput at 64 - 1024
+                               segments of a MoL model with rnn = fc = 256 (93 -> 52 us per step), 1.71 - 1.72 x for 10-bit RAW at 512 (306 -> 178), 2.03 - 2.05 x
+                               for MoL at 576 (417 -> 205) */
     WRNN_ALGO_SPARSE = 5    /* block-sparse GRU kernel (MOL, BASELINE config 5; or 9-bit RAW = 512 classes -- fc3 a dense stage of every workgroup,
                                four sampling workgroups per cluster): needs GRU matrices whose 16x1 block rows keep <= 64 columns
                                (wrnn_pack_sparse_blocks) and >= 256 CUs; fc1 / fc2 are gathered too when they are block-sparse (wrnn_pack_sparse_fc_blocks); 16 clusters of 16 CUs, ONE group of <= 16 segments each: a
@@ -260,6 +276,15 @@ int wrnn_pack_sparse_fc_blocks(const wrnn_pack *p);
  * kept / total (either may be NULL): surviving and all 16x1 blocks of rnn1.weight_ih, rnn1.weight_hh, rnn2.weight_ih, rnn2.weight_hh, fc1.weight, fc2.weight
  * (0 / 0 where the matrix's rows per gate are no multiple of 16: nothing was counted). */
 int wrnn_pack_tile_sparse(const wrnn_pack *p, int32_t kept[6], int32_t total[6]);
+/* The bf16 view of a generic pack (WRNN_ALGO_TILE_BF16): its bytes, 0 for none -- a pack of the shipped dims, dims past the LDS rule, or a weight that is
+ * not finite or rounds to +-inf in bfloat16 (wrnn_pack_create still succeeds, and wrnn_last_error() names the matrix). */
+size_t wrnn_pack_tile_bf16(const wrnn_pack *p);
+/* Test hook, host only (no device, the HIP runtime is not touched): the packing routine of the bf16 view on ONE row-major matrix W [rows][K].  Returns the
+ * number of bf16 elements of the image (or WRNN_ERR_ARG: a value is not finite or rounds to +-inf) and, when `out` is non-NULL and the image fits `cap`
+ * elements, fills
+ *   out  [ceil(K / 32)][rows][4 kq][8 j]   W[row][32 s + 4 j + kq] rounded to bfloat16, round-to-nearest-even; k >= K: +0
+ * followed by 64 rows (2048 elements) of +0 (csrc/wrnn_tile_bf16.hip: what a lane loads, and why). */
+int wrnn_debug_tile_bf16_pack(const float *W, int32_t rows, int32_t K, uint16_t *out, size_t cap);
 /* Test hook, host only (no device, the HIP runtime is not touched): the packing routine of the tile-sparse view on ONE row-major matrix W [rows][K] of
  * `gates` gates (rows / gates a multiple of 16).  Returns the number of 16-column GROUPS of the packed lists (or WRNN_ERR_ARG) and fills
  *   tab   [rows / 16][2]        per block row: the first group of its list | its surviving columns n (ascending; groups: (n + 15) / 16)
@@ -386,7 +411,9 @@ typedef struct wrnn_plan_traits {
                                   < 0: none, -(1 + 1001 m + f) names the first GRU matrix m (0 rnn1 ih, 1 rnn1 hh, 2 rnn2 ih, 3 rnn2 hh) that keeps more than
                                   41 % of its blocks and its surviving fraction f in 1/1000 (a message only); 0: none (gH % 16, or nothing recorded) */
     int32_t sp_max_blocks;     /* |wrnn_pack_sparse_blocks()| (a message only) */
-    int32_t sp_fc;             /* 1: fc1 / fc2 are block-sparse too (wrnn_pack_sparse_fc_blocks() > 0).  Recorded; no planning decision reads it */
+    int32_t sp_fc;             /* bit 0: fc1 / fc2 are block-sparse too (wrnn_pack_sparse_fc_blocks() > 0).  Recorded; no planning decision reads it.
+                                  bit 1 (a GENERIC pack): it has NO bf16 view although its dims pass the LDS rule (a weight rounds to +-inf): WRNN_ALGO_TILE_BF16
+                                  refuses it.  Otherwise a generic pack has the view exactly when WRNN_ALGO_TILE admits its dims */
 } wrnn_plan_traits;
 /* What wrnn_plan_segments (`out`) and wrnn_workspace_bytes_segments (`workspace_bytes`) answer for a pack with these traits: the same
  * code, return codes and wrnn_last_error() texts, with neither a pack nor a device -- the HIP runtime is not touched.  A step range in

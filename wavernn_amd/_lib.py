@@ -17,13 +17,13 @@ ERR_NO_DEVICE = -2          # WRNN_ERR_NO_DEVICE
 ERR_RESIDENCY = -6          # WRNN_ERR_RESIDENCY: the persistent grid cannot be co-resident on this device
 MODE_RAW, MODE_MOL = 0, 1
 ABI_VERSION = 9
-ALGO_AUTO, ALGO_STREAM, ALGO_LOOP, ALGO_SPARSE, ALGO_DUO, ALGO_CHAIN, ALGO_OCTO, ALGO_TILE, ALGO_TILE_SPARSE = 0, 1, 2, 5, 6, 7, 8, 10, 12
+ALGO_AUTO, ALGO_STREAM, ALGO_LOOP, ALGO_SPARSE, ALGO_DUO, ALGO_CHAIN, ALGO_OCTO, ALGO_TILE, ALGO_TILE_SPARSE, ALGO_TILE_BF16 = 0, 1, 2, 5, 6, 7, 8, 10, 12, 13
 ALGOS = {'auto': ALGO_AUTO, 'stream': ALGO_STREAM, 'loop': ALGO_LOOP, 'sparse': ALGO_SPARSE, 'duo': ALGO_DUO, 'chain': ALGO_CHAIN, 'octo': ALGO_OCTO, 'tile': ALGO_TILE,
-         'tile_sparse': ALGO_TILE_SPARSE}
+         'tile_sparse': ALGO_TILE_SPARSE, 'tile_bf16': ALGO_TILE_BF16}
 
 #: every symbol include/wavernn_amd.h declares
 EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_create', 'wrnn_pack_destroy',
-           'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_pack_tile_sparse', 'wrnn_debug_tile_sparse_pack', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
+           'wrnn_pack_weight_bytes', 'wrnn_pack_sparse_blocks', 'wrnn_pack_sparse_fc_blocks', 'wrnn_pack_tile_sparse', 'wrnn_pack_tile_bf16', 'wrnn_debug_tile_bf16_pack', 'wrnn_debug_tile_sparse_pack', 'wrnn_workspace_bytes', 'wrnn_workspace_bytes_segments', 'wrnn_generate',
            'wrnn_generate_segments', 'wrnn_noise_fill', 'wrnn_noise_fill_host', 'wrnn_nll', 'wrnn_nll_host', 'wrnn_plan_segments', 'wrnn_status', 'wrnn_timer_create', 'wrnn_timer_destroy', 'wrnn_timer_ms',
            'wrnn_timer_launches', 'wrnn_debug_read_exchange', 'wrnn_debug_plan', 'wrnn_selftest', 'wrnn_selftest_metric', 'wrnn_pre_create',
            'wrnn_pre_destroy', 'wrnn_pre_hop', 'wrnn_pre_workspace_bytes', 'wrnn_pre_upsample', 'wrnn_pre_upsample_rows', 'wrnn_pre_workspace_bytes_many',
@@ -245,6 +245,9 @@ def lib():
     L.wrnn_debug_tile_sparse_pack.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                               ctypes.POINTER(ctypes.c_int32)]
+    L.wrnn_pack_tile_bf16.argtypes = [ctypes.c_void_p]
+    L.wrnn_pack_tile_bf16.restype = ctypes.c_size_t
+    L.wrnn_debug_tile_bf16_pack.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t]
     L.wrnn_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(Geometry), ctypes.POINTER(Options)]
     L.wrnn_workspace_bytes.restype = ctypes.c_size_t
     L.wrnn_generate.argtypes = [ctypes.c_void_p, ctypes.POINTER(Geometry), ctypes.c_void_p, ctypes.c_void_p,
@@ -411,3 +414,18 @@ def tile_sparse_pack_host(W, gates):
     check(min(0, lib().wrnn_debug_tile_sparse_pack(W.ctypes.data, rows, K, gates, tab.ctypes.data, cols.ctypes.data, vals.ctypes.data, groups,
                                                    ctypes.byref(kept), ctypes.byref(total), ctypes.byref(adm))), 'wrnn_debug_tile_sparse_pack')
     return dict(tab=tab, cols=cols, vals=vals, kept=int(kept.value), total=int(total.value), admitted=bool(adm.value))
+
+
+def tile_bf16_pack_host(W):
+    """`wrnn_debug_tile_bf16_pack`: the bf16 image (WRNN_ALGO_TILE_BF16) of one float32 matrix W (rows, K) as the library packs it: a uint16 array
+    (ceil(K / 32) * rows + 64, 4, 8) -- [s * rows + row][kq][j] holds W[row][32 s + 4 j + kq] rounded to bfloat16 (round-to-nearest-even), k >= K and the
+    last 64 rows +0.  Raises WrnnError when a value is not finite or rounds to +-inf.  No HIP device is needed."""
+    import numpy as np
+    W = np.ascontiguousarray(W, np.float32)
+    rows, K = W.shape
+    n = lib().wrnn_debug_tile_bf16_pack(W.ctypes.data, rows, K, None, 0)
+    if n < 0:
+        check(n, 'wrnn_debug_tile_bf16_pack')
+    out = np.full(n, 0xFFFF, np.uint16)
+    check(min(0, lib().wrnn_debug_tile_bf16_pack(W.ctypes.data, rows, K, out.ctypes.data, n)), 'wrnn_debug_tile_bf16_pack')
+    return out.reshape(-1, 4, 8)

@@ -10,7 +10,7 @@ echo "$FLAGS" > $OBJ/.flags.new
 if ! cmp -s $OBJ/.flags.new $OBJ/.flags 2>/dev/null; then rm -f $OBJ/*.o; mv $OBJ/.flags.new $OBJ/.flags; fi
 NEWEST_H=$(ls -t *.h ../../include/*.h | head -1)
 pids=()
-SRCS="wrnn_abi wrnn_noise wrnn_nll wrnn_cond wrnn_stream wrnn_generic wrnn_tile wrnn_tile_sparse wrnn_loop wrnn_duo wrnn_octo wrnn_chain wrnn_sparse wrnn_pre wrnn_post wrnn_taco wrnn_taco_batch wrnn_cbhg wrnn_selftest"
+SRCS="wrnn_abi wrnn_noise wrnn_nll wrnn_cond wrnn_stream wrnn_generic wrnn_tile wrnn_tile_sparse wrnn_tile_bf16 wrnn_loop wrnn_duo wrnn_octo wrnn_chain wrnn_sparse wrnn_pre wrnn_post wrnn_taco wrnn_taco_batch wrnn_cbhg wrnn_selftest"
 for f in $SRCS; do
   if [ ! -f $OBJ/$f.o ] || [ $f.hip -nt $OBJ/$f.o ] || [ $NEWEST_H -nt $OBJ/$f.o ]; then
     $HIPCC $FLAGS -c $f.hip -o $OBJ/$f.o & pids+=($!)

@@ -33,6 +33,7 @@ hipError_t launch_tile(const GenArgs &args, int mode, hipStream_t stream);
 size_t tile_lds_bytes(int H, int F, int M, int A, int C);
 bool tile_dims_ok(int H, int F, int M, int A, int C, int mode);
 hipError_t launch_tile_sparse(const GenArgs &args, const TileSparseArgs &sp, int mode, bool fcs, hipStream_t stream);
+hipError_t launch_tile_bf16(const GenArgs &args, const TileBf16Args &bw, int mode, hipStream_t stream);
 hipError_t launch_duo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
 int duo_max_depth();
 size_t duo_xbuf_bytes(int G);
@@ -95,6 +96,9 @@ struct wrnn_pack {
     int ts_view;
     int32_t ts_kept[6], ts_total[6];
     TileSparseArgs ts;
+    // ... and its bf16 view (wrnn_tile_bf16.hip): the eight matrices rounded to bfloat16; bf_bytes == 0: none
+    size_t bf_bytes;
+    TileBf16Args bf;
     const float *sp_vals;
     const int *sp_cols;
     int sp_fc_max_blocks;      // fc1 / fc2 (columns [0, H): the aux columns live in the per-frame tables): largest block row
@@ -177,7 +181,39 @@ void tile_sparse_pack(const float *W, int rows, int K, TileSparsePacked &o)
 // per-gate rounding keeps 40.01 %, is the least sparse one at which wrnn_tile_sparse_kernel measured no slower than wrnn_tile_kernel (profiles/tile_sparse_ab.json:
 // 91.8 vs 92.6 us per step; at 50 % it is 0.87 x)
 bool tile_sparse_admits(int kept, int total) { return total > 0 && 100 * (long)kept <= 41 * (long)total; }
+
+// The bf16 image of one matrix W [rows][K] (row-major): the layout wrnn_tile_bf16.hip describes -- [k / 32][row][k % 4][(k % 32) / 4], the weights rounded to
+// bfloat16 round-to-nearest-even, k >= K and the 64 rows behind the last k-step +0.  false: a value is not finite, or rounds to +-inf.  Host only.
+constexpr int BF16_TAIL_ROWS = 64;
+bool tile_bf16_pack(const float *W, int rows, int K, std::vector<uint16_t> &o)
+{
+    const int nsteps = (K + 31) / 32;
+    o.assign(((size_t)nsteps * rows + BF16_TAIL_ROWS) * 32, 0);
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < K; ++k) {
+            uint32_t u;
+            memcpy(&u, W + (size_t)r * K + k, sizeof u);
+            if ((u & 0x7F800000u) == 0x7F800000u) return false;
+            const uint32_t q = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+            if ((q & 0x7F80u) == 0x7F80u) return false;
+            o[(((size_t)(k >> 5) * rows + r) * 4 + (k & 3)) * 8 + ((k & 31) >> 2)] = (uint16_t)q;
+        }
+    return true;
+}
 }  // namespace
+
+extern "C" int wrnn_debug_tile_bf16_pack(const float *W, int32_t rows, int32_t K, uint16_t *out, size_t cap)
+{
+    if (!W || rows < 1 || K < 1) { set_err("bad argument"); return WRNN_ERR_ARG; }
+    if (((size_t)(K + 31) / 32 * rows + BF16_TAIL_ROWS) * 32 > 0x7FFFFFFFu) { set_err("%d x %d: more than 2^31 elements", rows, K); return WRNN_ERR_ARG; }
+    std::vector<uint16_t> img;
+    if (!tile_bf16_pack(W, rows, K, img)) {
+        set_err("a weight is not finite or rounds to +-inf in bfloat16 (its magnitude is above 3.3895e38): no bf16 image");
+        return WRNN_ERR_ARG;
+    }
+    if (out && img.size() <= cap) memcpy(out, img.data(), img.size() * sizeof(uint16_t));
+    return (int)img.size();
+}
 
 extern "C" int wrnn_debug_tile_sparse_pack(const float *W, int32_t rows, int32_t K, int32_t gates, int32_t *tab, int32_t *cols, float *vals,
                                            int32_t group_capacity, int32_t *kept, int32_t *total, int32_t *admitted)
@@ -253,6 +289,23 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
             ts_off[m][1] = b.add(reinterpret_cast<const float *>(ts_pk[m].cols.data()), ts_pk[m].cols.size());
             ts_off[m][2] = b.add(reinterpret_cast<const float *>(ts_pk[m].tab.data()), ts_pk[m].tab.size());
         }
+        // ---- the bf16 view (wrnn_tile_bf16.hip): every pack whose dims pass wrnn_tile_kernel's LDS rule, unless a weight rounds to +-inf
+        const float *bf_src[8] = {w->I_w, w->w_ih1, w->w_hh1, w->w_ih2, w->w_hh2, w->fc1_w, w->fc2_w, w->fc3_w};
+        const int bf_rows[8] = {gH, 3 * gH, 3 * gH, 3 * gH, 3 * gH, gF, gF, C}, bf_K[8] = {1 + gM + gA, gH, gH, gH + gA, gH, gH + gA, gF + gA, gF};
+        static const char *const bf_names[8] = {"I.weight", "rnn1.weight_ih", "rnn1.weight_hh", "rnn2.weight_ih", "rnn2.weight_hh", "fc1.weight", "fc2.weight", "fc3.weight"};
+        size_t bf_off[8] = {0}, bf_bytes = 0;
+        bool bf_view = tile_dims_ok(gH, gF, gM, gA, C, w->mode), bf_inf = false;
+        for (int m = 0; m < 8 && bf_view; ++m) {      // (uint16 pairs stored in the float builder; an image is a whole number of 64-byte rows)
+            std::vector<uint16_t> img;
+            if (!tile_bf16_pack(bf_src[m], bf_rows[m], bf_K[m], img)) {
+                // not an error: the pack runs on every other kernel.  The text is what wrnn_last_error() answers after this call
+                set_err("wrnn_pack_create: no bf16 view -- a value of %s is not finite or rounds to +-inf in bfloat16; algo tile_bf16 will refuse this pack", bf_names[m]);
+                bf_view = false; bf_inf = true; bf_bytes = 0;
+                break;
+            }
+            bf_off[m] = b.add(reinterpret_cast<const float *>(img.data()), img.size() / 2);
+            bf_bytes += img.size() * sizeof(uint16_t);
+        }
         b.add(nullptr, 64);
         wrnn_pack *p = new wrnn_pack();
         memset(p, 0, sizeof *p);
@@ -281,6 +334,10 @@ extern "C" int wrnn_pack_create(const wrnn_weights *w, int device, wrnn_pack **o
         // what the planner reads of it (wrnn_plan_traits of a GENERIC pack): sp_nbp > 0 a view, sp_fc its fc half; sp_nbp < 0 names the first matrix that
         // keeps too many of its blocks, -(1 + 1001 m + its surviving fraction in 1/1000, rounded up)
         p->tr.sp_nbp = ts_view ? 1 : 0; p->tr.sp_fc = ts_view == 2 ? 1 : 0;
+        // the bf16 view: the planner derives it from the dims (tile_dims_ok); bit 1 of sp_fc says that it is missing all the same
+        p->bf_bytes = bf_view ? bf_bytes : 0;
+        for (int m = 0; m < 8 && bf_view; ++m) p->bf.m[m] = reinterpret_cast<const uint16_t *>(base + bf_off[m]);
+        if (bf_inf) p->tr.sp_fc |= 2;
         for (int m = 0; m < 4 && !ts_view && gH % 16 == 0; ++m)
             if (!tile_sparse_admits(ts_kept[m], ts_total[m])) {
                 p->tr.sp_nbp = -(1 + 1001 * m + (int)(((long)ts_kept[m] * 1000 + ts_total[m] - 1) / ts_total[m]));
@@ -463,6 +520,8 @@ extern "C" int wrnn_pack_tile_sparse(const wrnn_pack *p, int32_t kept[6], int32_
     return p->tr.generic ? p->ts_view : 0;
 }
 
+extern "C" size_t wrnn_pack_tile_bf16(const wrnn_pack *p) { return p && p->tr.generic ? p->bf_bytes : 0; }
+
 struct wrnn_timer {
     int device;
     std::vector<hipEvent_t> ev;     // pairs (start, stop), grown on demand and reused
@@ -542,7 +601,7 @@ int enqueue_progress(const wrnn_options *o, int done, int T, int n, hipStream_t 
     return WRNN_OK;
 }
 
-enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, K_TILE_SPARSE, N_KINDS };
+enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, K_TILE_SPARSE, K_TILE_BF16, N_KINDS };
 constexpr int DUO_TAB_FPS = 8;       // rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
 constexpr bool DUO_AUTO = true;      // `auto` runs MoL on wrnn_duo_kernel at every depth (round 4, profiles/r04a_probe_new.json: 13.5 vs 16.6 us per step
                                      // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
@@ -591,6 +650,8 @@ const KindDesc KINDS[N_KINDS] = {
     /* K_TILE    */ {"wrnn_tile_kernel", 16, 0, false, false, false},
     // (wrnn_tile_kernel with the GRU -- and fc1 / fc2 -- stages on the pack's tile-sparse view; on request)
     /* K_TILE_SPARSE */ {"wrnn_tile_sparse_kernel", 16, 0, false, false, false},
+    // (wrnn_tile_kernel with the eight matrices in bfloat16, on the bf16 MFMA; on request)
+    /* K_TILE_BF16 */ {"wrnn_tile_bf16_kernel", 16, 0, false, false, false},
 };
 
 // what a call will run: kernel, split, rounds, slab length
@@ -683,7 +744,7 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     const bool partial = pl->t0 != 0 || pl->t1 != T;
     const int algo = o->algo;
     if (algo != WRNN_ALGO_AUTO && algo != WRNN_ALGO_STREAM && algo != WRNN_ALGO_LOOP && algo != WRNN_ALGO_SPARSE && algo != WRNN_ALGO_DUO && algo != WRNN_ALGO_CHAIN &&
-        algo != WRNN_ALGO_OCTO && algo != WRNN_ALGO_TILE && algo != WRNN_ALGO_TILE_SPARSE) {
+        algo != WRNN_ALGO_OCTO && algo != WRNN_ALGO_TILE && algo != WRNN_ALGO_TILE_SPARSE && algo != WRNN_ALGO_TILE_BF16) {
         set_err("unknown algo %d", algo);
         return WRNN_ERR_ARG;
     }
@@ -739,6 +800,27 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
         if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
         if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_sparse_kernel)"); return WRNN_ERR_ARG; }
         pl->kind = K_TILE_SPARSE;
+        return WRNN_OK;
+    }
+    if (algo == WRNN_ALGO_TILE_BF16) {          // on request only: wrnn_tile_kernel on the pack's bf16 view (csrc/wrnn_tile_bf16.hip)
+        if (!p->generic) {
+            set_err("wrnn_tile_bf16_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo auto "
+                    "picks its kernel", H);
+            return WRNN_ERR_ARG;
+        }
+        if (!tile_dims_ok(p->gH, p->gF, p->gM, p->gA, p->C, p->mode)) {
+            set_err("wrnn_tile_bf16_kernel: rnn %d, fc %d, feat %d, aux %d, %d classes need %zu bytes of LDS per workgroup, the limit is %d (and RAW: <= 2048 classes); "
+                    "algo auto runs this pack on wrnn_generic_kernel", p->gH, p->gF, p->gM, p->gA, p->C, tile_lds_bytes(p->gH, p->gF, p->gM, p->gA, p->C), 160 * 1024);
+            return WRNN_ERR_ARG;
+        }
+        if (p->sp_fc & 2) {
+            set_err("wrnn_tile_bf16_kernel: this pack has no bf16 view (wrnn_pack_tile_bf16() == 0) -- one of its weights is not finite or rounds to +-inf in "
+                    "bfloat16; algo tile runs it in float32");
+            return WRNN_ERR_ARG;
+        }
+        if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
+        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_bf16_kernel)"); return WRNN_ERR_ARG; }
+        pl->kind = K_TILE_BF16;
         return WRNN_OK;
     }
     if (p->generic) {           // non-shipped hparams: the dimension-generic kernel is the only one that takes them without being asked for by name
@@ -847,7 +929,7 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
     l.xcc = o;    o = al(o + XCC_WORDS * sizeof(unsigned));
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16) {
         l.nlib = o; if (noise_lib) o = al(o + (size_t)T * noise_row);
         l.total = o;
         return l;
@@ -1021,7 +1103,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         HIPCHK(hipMemcpyAsync(ws + l.segs + (size_t)2 * B * sizeof(int), o->seg_moff, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
         HIPCHK(launch_put_floats((float *)(ws + l.melc), coef, 3 * LAST_SCALE, stream));       // (by value, as kernel arguments: `coef` is a stack array)
     }
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16) {
         GenArgs g;
         memset(&g, 0, sizeof g);
         g.I_T = p->g_I_T; g.I_b = p->I_b; g.w_ih1T = p->w_ih1T; g.w_hh1T = p->w_hh1T; g.b_ih1 = p->b_ih1; g.b_hh1 = p->b_hh1;
@@ -1036,7 +1118,9 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         if (pl.kind == K_TILE_SPARSE && !p->ts_view) { set_err("this pack has no tile-sparse view"); return WRNN_ERR_ARG; }      // (the planner's traits are the pack's own: never)
-        HIPCHK(pl.kind == K_TILE_SPARSE ? launch_tile_sparse(g, p->ts, p->tr.mode, p->ts_view == 2, stream)
+        if (pl.kind == K_TILE_BF16 && !p->bf_bytes) { set_err("this pack has no bf16 view"); return WRNN_ERR_ARG; }             // (likewise)
+        HIPCHK(pl.kind == K_TILE_BF16   ? launch_tile_bf16(g, p->bf, p->tr.mode, stream)
+               : pl.kind == K_TILE_SPARSE ? launch_tile_sparse(g, p->ts, p->tr.mode, p->ts_view == 2, stream)
                : pl.kind == K_TILE      ? launch_tile(g, p->tr.mode, stream)
                                         : launch_generic(g, p->tr.mode, stream));
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;

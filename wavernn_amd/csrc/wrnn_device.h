@@ -163,6 +163,12 @@ struct TileSparseArgs {
     TileSparseMat m[6];                 // w_ih1, w_hh1, w_ih2, w_hh2, fc1, fc2 (the last two: only with the fc view)
 };
 
+// The bf16 view of a generic pack (wrnn_tile_bf16.hip, whose header describes the image of one matrix; built by tile_bf16_pack of wrnn_abi.hip): the eight
+// loop matrices rounded to bfloat16, round-to-nearest-even
+struct TileBf16Args {
+    const uint16_t *m[8];               // I, w_ih1, w_hh1, w_ih2, w_hh2, fc1, fc2, fc3
+};
+
 // arguments of the hoisted-conditioning kernels (wrnn_cond.hip)
 struct CondArgs {
     const float *mels_up;   // [L][MEL]

@@ -31,11 +31,17 @@ namespace wrnn {
 template <int MODE>
 __global__ __launch_bounds__(TNT) void wrnn_tile_kernel(const GenArgs a)
 {
+#define TILE_STAGE_I(x, dst) tile_linear<false>(a.I_T, a.I_b, H, K0, x, dst, w, lane)
 #define TILE_STAGE_RNN1(x, hs, dst) tile_gru(a.w_ih1T, a.w_hh1T, a.b_ih1, a.b_hh1, H, H, x, hs, dst, w, lane)
 #define TILE_STAGE_RNN2(x, hs, dst) tile_gru(a.w_ih2T, a.w_hh2T, a.b_ih2, a.b_hh2, H, H + A, x, hs, dst, w, lane)
 #define TILE_STAGE_FC1(x, dst) tile_linear<true>(a.fc1T, a.fc1_b, F, H + A, x, dst, w, lane)
 #define TILE_STAGE_FC2(x, dst) tile_linear<true>(a.fc2T, a.fc2_b, F, F + A, x, dst, w, lane)
+#define TILE_FC3_TILE(row0, x, acc) tile_dot<1, 32, 1>(a.fc3T, C, 0, row0, F, x, lane, acc)
+#define TILE_FC3_GROUP(row0, x, acc) tile_dot<1, 16, 4>(a.fc3T, C, 0, row0, F, x, lane, acc)
 #include "wrnn_tile_body.inc"
+#undef TILE_STAGE_I
+#undef TILE_FC3_TILE
+#undef TILE_FC3_GROUP
 #undef TILE_STAGE_RNN1
 #undef TILE_STAGE_RNN2
 #undef TILE_STAGE_FC1

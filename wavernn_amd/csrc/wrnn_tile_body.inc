@@ -1,8 +1,11 @@
 // wrnn_tile_body.inc -- the body of a loop kernel of the 16-segment tile dataflow (wrnn_tile.hip describes it): the LDS carve, then per step the conditioning,
 // the I layer, rnn1, rnn2, fc1, fc2, fc3 and the sampling.  Included INSIDE a kernel `template <int MODE> ... (const GenArgs a ...)` of TNT threads, after the
-// kernel has defined the four stages between the I layer and fc3 as macros over the names of this body (a, H, F, A, w, lane):
+// kernel has defined the matrix products as macros over the names of this body (a, H, F, A, C, K0, w, lane):
+//   TILE_STAGE_I(x, dst)                                        W_I . x + b -> dst
 //   TILE_STAGE_RNN1(x, hs, dst)  TILE_STAGE_RNN2(x, hs, dst)    one GRU stage on input vector x and state hs, the new h -> dst
 //   TILE_STAGE_FC1(x, dst)       TILE_STAGE_FC2(x, dst)         relu(W . x + b) -> dst
+//   TILE_FC3_TILE(row0, x, acc)                                 MOL: fc3 rows row0 .. row0 + 15 (consecutive) . x -> f32x4 acc[1]
+//   TILE_FC3_GROUP(row0, x, acc)                                RAW: fc3 rows row0 .. row0 + 63 as four interleaved tiles . x -> f32x4 acc[4]
 // Text, not a function: wrnn_tile_kernel, which was written first, compiles to the code object it had before wrnn_tile_sparse_kernel shared this body.
 
     extern __shared__ __attribute__((aligned(16))) float tsm[];
@@ -30,7 +33,7 @@
         }
         __syncthreads();
         // ---- I (:208-209): xi -> vb[0..H)
-        tile_linear<false>(a.I_T, a.I_b, H, K0, in0, vb, w, lane);
+        TILE_STAGE_I(in0, vb);
         __syncthreads();
         // ---- rnn1 (:210) on xi; the new h1 -> va[0..H), then h1 <- it and x1 = xi + h1 (:212) -> va[0..H)
         TILE_STAGE_RNN1(vb, h1s, va);
@@ -58,7 +61,7 @@
         if (MODE == 1) {                                // utils/distribution.py:102-121 (C = 30: 10 mixtures); logits -> red[c][seg]
             for (int tile = w; tile * 16 < C; tile += TNW) {
                 f32x4 acc[1];
-                tile_dot<1, 32, 1>(a.fc3T, C, 0, tile * 16, F, vb, lane, acc);
+                TILE_FC3_TILE(tile * 16, vb, acc);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int c = tile * 16 + q4 + v;
@@ -109,7 +112,7 @@
                 for (int j = 0; j < 4; ++j) keep[q][j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
                 if (grp * 64 < C) {
                     f32x4 acc[4];
-                    tile_dot<1, 16, 4>(a.fc3T, C, 0, grp * 64, F, vb, lane, acc);
+                    TILE_FC3_GROUP(grp * 64, vb, acc);
 #pragma unroll
                     for (int v = 0; v < 4; ++v)
 #pragma unroll

@@ -119,6 +119,7 @@ __device__ __forceinline__ void ts_linear(const TileSparseMat &fc, const float *
 template <int MODE, bool FCS>
 __global__ __launch_bounds__(TNT) void wrnn_tile_sparse_kernel(const GenArgs a, const TileSparseArgs sp)
 {
+#define TILE_STAGE_I(x, dst) tile_linear<false>(a.I_T, a.I_b, H, K0, x, dst, w, lane)
 #define TILE_STAGE_RNN1(x, hs, dst) ts_gru(sp.m[0], sp.m[1], a.b_ih1, a.b_hh1, H, x, hs, dst, w, lane)
 #define TILE_STAGE_RNN2(x, hs, dst) ts_gru(sp.m[2], sp.m[3], a.b_ih2, a.b_hh2, H, x, hs, dst, w, lane)
 #define TILE_STAGE_FC1(x, dst)                                                  \
@@ -131,7 +132,12 @@ __global__ __launch_bounds__(TNT) void wrnn_tile_sparse_kernel(const GenArgs a, 
         if constexpr (FCS) ts_linear(sp.m[5], a.fc2_b, F, x, dst, w, lane);      \
         else tile_linear<true>(a.fc2T, a.fc2_b, F, F + A, x, dst, w, lane);      \
     } while (0)
+#define TILE_FC3_TILE(row0, x, acc) tile_dot<1, 32, 1>(a.fc3T, C, 0, row0, F, x, lane, acc)
+#define TILE_FC3_GROUP(row0, x, acc) tile_dot<1, 16, 4>(a.fc3T, C, 0, row0, F, x, lane, acc)
 #include "wrnn_tile_body.inc"
+#undef TILE_STAGE_I
+#undef TILE_FC3_TILE
+#undef TILE_FC3_GROUP
 #undef TILE_STAGE_RNN1
 #undef TILE_STAGE_RNN2
 #undef TILE_STAGE_FC1

@@ -131,6 +131,11 @@ class LoopEngine:
         view = int(self.lib.wrnn_pack_tile_sparse(self._pack, ctypes.byref(kept), ctypes.byref(total)))
         return view, [int(k) for k in kept], [int(t) for t in total]
 
+    def tile_bf16_bytes(self):
+        """`wrnn_pack_tile_bf16`: bytes of the pack's bf16 view; 0 -- algo='tile_bf16' refuses this pack: the shipped dims, dims past wrnn_tile_kernel's
+        LDS rule, or a weight that rounds to +-inf in bfloat16."""
+        return int(self.lib.wrnn_pack_tile_bf16(self._pack))
+
     @property
     def weight_bytes(self):
         return int(self.lib.wrnn_pack_weight_bytes(self._pack))

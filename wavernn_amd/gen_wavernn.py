@@ -73,7 +73,8 @@ def main(argv=None):
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
                          "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
-                         "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones")
+                         "such model: it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the 16x1 blocks survive (sparsity >= 0.6), and skips the pruned ones; "
+                         "'tile_bf16' is 'tile' with the weights rounded to bfloat16 on the bf16 matrix pipe -- not the reference's arithmetic")
     ap.add_argument('--stream', action='store_true', help='--unbatched: hand the audio on in chunks while the loop goes on (WaveRNN.generate_stream); prints the time to the first chunk')
     ap.add_argument('--chunk-steps', type=int, default=2200, help='--stream: loop steps per chunk')
     ap.set_defaults(batched=True)

@@ -138,7 +138,8 @@ class WaveRNN(nn.Module):
         #: ... and the generator's key (wrnn_options.noise_seed), shared by every call of this model
         self.noise_key = 0
         #: 'auto' | 'loop' | 'sparse' | 'stream' | ... (`_lib.ALGOS`: WRNN_ALGO_*, include/wavernn_amd.h); 'tile' / 'tile_sparse' (pruned): a model of other dims than the shipped ones on
-        #: wrnn_tile_kernel (16 segments per workgroup) instead of `auto`'s wrnn_generic_kernel (one)
+        #: wrnn_tile_kernel (16 segments per workgroup) instead of `auto`'s wrnn_generic_kernel (one); 'tile_bf16': the same with the eight loop matrices rounded to
+        #: bfloat16 (wrnn_tile_bf16_kernel: NOT the reference's arithmetic -- `synthetic.bf16_round_state_dict` gives the model it runs)
         self.loop_algo = 'auto'
         #: 2 = a run planned on wrnn_sparse_kernel puts TWO groups of <= 16 segments on each of its 16 clusters (wrnn_options.sparse_groups: 512 segments a
         #: round instead of 256, the same samples; MoL models whose Linear layers are pruned too).  None (default) = one group.  A run on any other

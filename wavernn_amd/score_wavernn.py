@@ -39,7 +39,8 @@ def main(argv=None):
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--mu_law', action='store_true', help='RAW: mu-law encode the waveform (hparams.mu_law) instead of linear labels')
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS), help="the loop kernel (model.loop_algo); 'tile_sparse' scores a pruned model of other dims than the shipped ones on its surviving 16x1 blocks: "
-                         "it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the blocks survive (sparsity >= 0.6)")
+                         "it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the blocks survive (sparsity >= 0.6); "
+                         "'tile_bf16' scores such a model with its weights rounded to bfloat16: against --algo tile that is what the rounding costs, in bits per sample")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('wavernn_amd needs a HIP device; there is no CPU path (use the reference for that)')

@@ -78,6 +78,31 @@ def random_state_dict(seed, mode='MOL', rnn_dims=512, fc_dims=512, bits=9, pad=2
     return sd
 
 
+#: the eight matrices of the loop (what WRNN_ALGO_TILE_BF16 stores as bfloat16); biases and the up-sampling network are not among them
+BF16_MATRICES = ('I.weight', 'rnn1.weight_ih_l0', 'rnn1.weight_hh_l0', 'rnn2.weight_ih_l0', 'rnn2.weight_hh_l0', 'fc1.weight', 'fc2.weight', 'fc3.weight')
+
+
+def bf16_round(x):
+    """float32 array -> the same values rounded to bfloat16, round-to-nearest-even, as float32 (finite inputs)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+
+
+def bf16_round_state_dict(sd):
+    """The model `algo='tile_bf16'` (wrnn_tile_bf16_kernel) runs: a copy of state dict `sd` whose eight loop matrices are rounded to bfloat16 exactly as
+    wrnn_pack_create rounds them; every other tensor is the same object.  Loaded into any float32 path -- the reference, the oracle, `algo='tile'` -- it
+    reproduces the kernel's model."""
+    out = dict(sd)
+    for k in BF16_MATRICES:
+        v = sd[k]
+        if isinstance(v, np.ndarray):
+            out[k] = bf16_round(v)
+        else:                                       # a torch tensor
+            import torch
+            out[k] = torch.from_numpy(bf16_round(v.detach().cpu().numpy())).to(v.device)
+    return out
+
+
 def random_mel(seed, n_frames, n_mels=80):
     """U[0,1) mel of shape (n_mels, n_frames): satisfies the range check of `gen_wavernn.py:52-55`."""
     return np.random.RandomState(seed).uniform(0.0, 1.0, size=(n_mels, n_frames)).astype(np.float32)
