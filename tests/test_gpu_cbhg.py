@@ -22,7 +22,7 @@ TACO_TOL = 1e-6                         # tests/test_gpu_config3.py: the bound o
 MARGIN = 8.0
 ENC_N = (1, 2, 15, 16, 17, 33, 100)     # one position, shorter than the widest conv, both sides of a 16-position tile, several tiles
 POST_N = (1, 17, 200)
-VARIANTS = ('plain', 'negative_bank', 'random_bnorm')
+VARIANTS = ('plain', 'negative_bank', 'random_bnorm', 'rich')
 
 
 @functools.lru_cache(maxsize=None)
@@ -30,9 +30,15 @@ def _state_dict(variant='plain'):
     """`random_tacotron_state_dict(3, shapes)` as tests/test_gpu_config3.py::_tts builds it.  'negative_bank': every
     conv1d_bank.*.bnorm.bias = -0.5, so that bank values in front of the max-pool are negative (with the plain dict none is, and a
     zero-padded pool would pass unseen).  'random_bnorm' (beyond the issue's cases): random batch-norm weight / bias / running
-    statistics everywhere -- the plain dict's norms are identities, which a wrong scale / shift fold would survive."""
+    statistics everywhere -- the plain dict's norms are identities, which a wrong scale / shift fold would survive.  'rich':
+    `helpers.rich_tacotron_state_dict(5, shapes)` instead, the weights of tests/golden/tacotron_mirror.npz -- every bias vector (pre-net,
+    highways, both directions' b_ih and b_hh of the GRUs) random in +-0.1 as well as the batch norms; in the other three every bias is zero,
+    and a bias placed at a wrong offset of the device blob or added outside r * (W_hn h + b_hn) would pass."""
+    from helpers import rich_tacotron_state_dict
     from wavernn_amd.synthetic import random_tacotron_state_dict
     shapes = json.load(open(os.path.join(HERE, 'golden', 'tacotron_shapes.json')))
+    if variant == 'rich':
+        return rich_tacotron_state_dict(5, shapes)
     sd = random_tacotron_state_dict(3, shapes)
     g = torch.Generator().manual_seed(11)
     for k in sd:

@@ -107,13 +107,22 @@ def test_tacotron_decoder_kernel_stop_test_and_r(variant):
     assert np.abs(mel_c - mel_k).max() <= TACO_TOL and np.abs(attn_c - attn_k).max() <= TACO_TOL
 
 
-@pytest.mark.parametrize('T', [1, 74, 800])
-def test_cbhg_bigru_kernel_matches_torch_gru(T):
+@pytest.mark.parametrize('T, weights', [(T, w) for w in ('plain', 'rich') for T in (1, 74, 800)],
+                         ids=['1', '74', '800', 'rich-1', 'rich-74', 'rich-800'])
+def test_cbhg_bigru_kernel_matches_torch_gru(T, weights):
     """`wrnn_bigru` (one persistent workgroup per direction, W_hh in registers) against `nn.GRU(128, 128, bidirectional=True)`'s
     functional form on the device (MIOpen) and on the CPU (ATen: what the reference runs, models/tacotron.py:95 / :137): another
-    summation order, so a tolerance -- 2e-6 on |h| <= 1 over 800 recurrent steps."""
+    summation order, so a tolerance -- 2e-6 on |h| <= 1 over 800 recurrent steps.  'rich': the post-net GRU of
+    `helpers.rich_tacotron_state_dict(5)`, whose b_ih and b_hh are random in +-0.1 -- with the plain weights both are zero, and b_hn
+    inside r * (W_hn h + b_hn) is never seen."""
     dev = torch.device('cuda', 0)
-    tts = _tts(dev)
+    if weights == 'rich':
+        from helpers import rich_tacotron_state_dict
+        from wavernn_amd.tacotron import TacotronInference
+        tts = TacotronInference(rich_tacotron_state_dict(5, json.load(open(os.path.join(HERE, 'golden', 'tacotron_shapes.json')))), device=dev)
+        assert float(tts.p['postnet.rnn.bias_hh_l0'].abs().max()) > 0.05 and float(tts.p['postnet.rnn.bias_hh_l0_reverse'].abs().max()) > 0.05
+    else:
+        tts = _tts(dev)
     q = 'postnet.rnn.'
     flat = [tts.p[q + n_] for n_ in ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0', 'weight_ih_l0_reverse',
                                       'weight_hh_l0_reverse', 'bias_ih_l0_reverse', 'bias_hh_l0_reverse')]

@@ -3,9 +3,9 @@
 
 The `_many` kernels run the tile bodies of the single-sentence kernels with sentence-relative positions, so the bar is EXACT everywhere:
 `torch.equal` against the single-sentence entry point on that sentence alone (which tests/test_gpu_cbhg.py holds to its float64 yardstick).
-No tolerance is introduced here.  Weights: those of tests/test_gpu_cbhg.py in its three variants -- with 'negative_bank' a max-pool that
+No tolerance is introduced here.  Weights: those of tests/test_gpu_cbhg.py in its four variants -- with 'negative_bank' a max-pool that
 looked at the previous sentence's last row instead of -inf changes position 0 of every sentence but the first, with 'random_bnorm' a wrong
-scale / shift base does.
+scale / shift base does, and with 'rich' (every bias vector random too) so does a bias read at another sentence's offset.
 
 Every output buffer is allocated PAD rows longer than the call needs and filled with FILL; the workspace gets GUARD bytes behind the queried
 size.  The rows behind the last sentence and the guard must read back unchanged."""
@@ -160,8 +160,19 @@ def test_postnet_sentences_equal_the_single_call(variant):
 
 def test_bigru_many_equals_three_bigru_calls():
     """T = (1, 2, 19), random gi, the post-net's GRU weights: out of `wrnn_bigru_many` equals three `wrnn_bigru` calls on the slices."""
+    _bigru_many_equals_bigru_calls('plain')
+
+
+def test_bigru_many_equals_three_bigru_calls_with_a_recurrent_bias():
+    """The same on the 'rich' weights: b_hh of both directions random in +-0.1 (zero in the plain weights)."""
+    p = _device_tts('rich').p
+    assert float(p['postnet.rnn.bias_hh_l0'].abs().max()) > 0.05 and float(p['postnet.rnn.bias_hh_l0_reverse'].abs().max()) > 0.05
+    _bigru_many_equals_bigru_calls('rich')
+
+
+def _bigru_many_equals_bigru_calls(variant):
     from wavernn_amd import _lib
-    L, tts = _lib.lib(), _device_tts('plain')
+    L, tts = _lib.lib(), _device_tts(variant)
     dev, T = tts.device, (1, 2, 19)
     rows = sum(T)
     g = torch.Generator().manual_seed(17)

@@ -25,28 +25,32 @@ C_TEXT = ' '.join([B_TEXT] * 3)
 _MEMO = {}
 
 
-def _tts(r=1):
-    if ('tts', r) not in _MEMO:
+def _tts(r=1, weights='plain'):
+    """The suite's weights on the device; weights='rich': `helpers.rich_tacotron_state_dict(5)`, every bias and batch norm random
+    (tests/test_gpu_taco_rich.py)."""
+    if ('tts', r, weights) not in _MEMO:
+        from helpers import rich_tacotron_state_dict
         from wavernn_amd.synthetic import random_tacotron_state_dict
         from wavernn_amd.tacotron import TacotronInference
-        sd = random_tacotron_state_dict(3, json.load(open(os.path.join(HERE, 'golden', 'tacotron_shapes.json'))))
+        shapes = json.load(open(os.path.join(HERE, 'golden', 'tacotron_shapes.json')))
+        sd = rich_tacotron_state_dict(5, shapes) if weights == 'rich' else random_tacotron_state_dict(3, shapes)
         if r != 1:
             sd['decoder.r' if 'decoder.r' in sd else 'r'] = torch.tensor(r)
         tts = TacotronInference(sd, device=torch.device('cuda', 0))
         assert tts.r == r
-        _MEMO['tts', r] = tts
-    return _MEMO['tts', r]
+        _MEMO['tts', r, weights] = tts
+    return _MEMO['tts', r, weights]
 
 
-def _enc(text, r=1):
+def _enc(text, r=1, weights='plain'):
     """(seq, seq_proj) of a sentence, [n][256] each, computed once."""
-    if ('enc', text, r) not in _MEMO:
+    if ('enc', text, r, weights) not in _MEMO:
         from wavernn_amd.tacotron import text_to_ids
-        tts = _tts(r)
+        tts = _tts(r, weights)
         with torch.no_grad():
             seq, proj = tts.encode(text_to_ids(text))
-        _MEMO['enc', text, r] = (seq[0].contiguous(), proj[0].contiguous())
-    return _MEMO['enc', text, r]
+        _MEMO['enc', text, r, weights] = (seq[0].contiguous(), proj[0].contiguous())
+    return _MEMO['enc', text, r, weights]
 
 
 def _status(L, ws, stream):
@@ -56,14 +60,14 @@ def _status(L, ws, stream):
     return list(st4)
 
 
-def _single(text, max_steps, threshold, r=1):
+def _single(text, max_steps, threshold, r=1, weights='plain'):
     """`wrnn_taco_decode(variant=2)` of one sentence into FILLed buffers: (mel [max_steps][80][r], scores [max_steps][n], steps).  Computed once
-    per (sentence, limit, threshold, r) and shared."""
-    key = ('single', text, max_steps, threshold, r)
+    per (sentence, limit, threshold, r, weights) and shared."""
+    key = ('single', text, max_steps, threshold, r, weights)
     if key not in _MEMO:
         from wavernn_amd import _lib
-        L, tts, dev = _lib.lib(), _tts(r), torch.device('cuda', 0)
-        seq, proj = _enc(text, r)
+        L, tts, dev = _lib.lib(), _tts(r, weights), torch.device('cuda', 0)
+        seq, proj = _enc(text, r, weights)
         n = seq.size(0)
         mel = torch.full((max_steps, 80, r), FILL, device=dev)
         scores = torch.full((max_steps, n), FILL, device=dev)
@@ -82,12 +86,12 @@ def _single(text, max_steps, threshold, r=1):
     return _MEMO[key]
 
 
-def _batch(texts, max_steps, threshold, r=1):
+def _batch(texts, max_steps, threshold, r=1, weights='plain'):
     """`wrnn_taco_decode_batch` into FILLed buffers: [(mel, scores, steps)] per sentence; the status words must read clean."""
     from wavernn_amd import _lib
-    L, tts, dev = _lib.lib(), _tts(r), torch.device('cuda', 0)
+    L, tts, dev = _lib.lib(), _tts(r, weights), torch.device('cuda', 0)
     S = len(texts)
-    encs = [_enc(t, r) for t in texts]
+    encs = [_enc(t, r, weights) for t in texts]
     mels = [torch.full((m, 80, r), FILL, device=dev) for m in max_steps]
     scores = [torch.full((m, e[0].size(0)), FILL, device=dev) for m, e in zip(max_steps, encs)]
     done = torch.full((S,), -1, dtype=torch.int32, device=dev)
@@ -108,14 +112,14 @@ def _batch(texts, max_steps, threshold, r=1):
     return [(m.cpu().numpy(), a.cpu().numpy(), k) for m, a, k in zip(mels, scores, ks)]
 
 
-def _assert_equal_to_single(texts, max_steps, threshold, r=1, expect=None):
-    outs = _batch(texts, max_steps, threshold, r)
+def _assert_equal_to_single(texts, max_steps, threshold, r=1, expect=None, weights='plain'):
+    outs = _batch(texts, max_steps, threshold, r, weights)
     steps = tuple(k for _, _, k in outs)
     print('steps_done', steps)
     if expect is not None:
         assert steps == tuple(expect), steps
     for text, limit, (mel, sc, k) in zip(texts, max_steps, outs):
-        mel1, sc1, k1 = _single(text, limit, threshold, r)
+        mel1, sc1, k1 = _single(text, limit, threshold, r, weights)
         assert k == k1, (text[:20], k, k1)
         print(f'{len(text):4d} chars: {k} steps, max |batch - single| mel {np.abs(mel[:k] - mel1[:k]).max():.3e} attention {np.abs(sc[:k] - sc1[:k]).max():.3e}')
         assert np.array_equal(mel[:k], mel1[:k]), text[:20]

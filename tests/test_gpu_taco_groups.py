@@ -24,12 +24,12 @@ THRESHOLD = 0.0146
 _MEMO = {}
 
 
-def _free_call(texts, max_steps, threshold, r):
+def _free_call(texts, max_steps, threshold, r, weights='plain'):
     """A `wrnn_taco_batch_call` over FILLed buffers and a workspace of its own: (struct, workspace, mels, scores, steps_done, keep-alive)."""
     from wavernn_amd import _lib
-    L, tts, dev = _lib.lib(), _tts(r), torch.device('cuda', 0)
+    L, tts, dev = _lib.lib(), _tts(r, weights), torch.device('cuda', 0)
     S = len(texts)
-    encs = [_enc(t, r) for t in texts]
+    encs = [_enc(t, r, weights) for t in texts]
     mels = [torch.full((m, 80, r), FILL, device=dev) for m in max_steps]
     scores = [torch.full((m, e[0].size(0)), FILL, device=dev) for m, e in zip(max_steps, encs)]
     done = torch.full((S,), -1, dtype=torch.int32, device=dev)
@@ -59,37 +59,37 @@ def _free_read(call):
     return out
 
 
-def _plain_free(texts, max_steps, threshold=THRESHOLD, r=1):
+def _plain_free(texts, max_steps, threshold=THRESHOLD, r=1, weights='plain'):
     """The plain `wrnn_taco_decode_batch` call on one group alone: computed once per group and shared."""
-    key = ('free', tuple(texts), tuple(max_steps), threshold, r)
+    key = ('free', tuple(texts), tuple(max_steps), threshold, r, weights)
     if key not in _MEMO:
         from wavernn_amd import _lib
-        call = _free_call(texts, max_steps, threshold, r)
-        rc = _lib.lib().wrnn_taco_decode_batch(0, ctypes.byref(_tts(r).decoder_weights()), ctypes.byref(call[0]))
+        call = _free_call(texts, max_steps, threshold, r, weights)
+        rc = _lib.lib().wrnn_taco_decode_batch(0, ctypes.byref(_tts(r, weights).decoder_weights()), ctypes.byref(call[0]))
         assert rc == _lib.WRNN_OK, _lib.lib().wrnn_taco_last_error()
         _MEMO[key] = _free_read(call)
     return _MEMO[key]
 
 
-def _grouped_free(groups, threshold=THRESHOLD, r=1):
+def _grouped_free(groups, threshold=THRESHOLD, r=1, weights='plain'):
     """`wrnn_taco_decode_batch_groups` over groups = [(texts, max_steps), ...]: per group [(mel, scores, steps)]."""
     from wavernn_amd import _lib
     L = _lib.lib()
-    calls = [_free_call(texts, max_steps, threshold, r) for texts, max_steps in groups]
+    calls = [_free_call(texts, max_steps, threshold, r, weights) for texts, max_steps in groups]
     table = (ctypes.POINTER(_lib.TacoBatchCall) * len(calls))(*[ctypes.pointer(call[0]) for call in calls])
-    rc = L.wrnn_taco_decode_batch_groups(0, ctypes.byref(_tts(r).decoder_weights()), table, len(calls))
+    rc = L.wrnn_taco_decode_batch_groups(0, ctypes.byref(_tts(r, weights).decoder_weights()), table, len(calls))
     assert rc == _lib.WRNN_OK, L.wrnn_taco_last_error()
     return [_free_read(call) for call in calls]
 
 
-def _assert_free_groups_equal_plain(groups, threshold=THRESHOLD, r=1, expect=None):
-    outs = _grouped_free(groups, threshold, r)
+def _assert_free_groups_equal_plain(groups, threshold=THRESHOLD, r=1, expect=None, weights='plain'):
+    outs = _grouped_free(groups, threshold, r, weights)
     steps = [tuple(k for _, _, k in out) for out in outs]
     print('steps_done', steps)
     if expect is not None:
         assert steps == [tuple(e) for e in expect], steps
     for g, ((texts, max_steps), out) in enumerate(zip(groups, outs)):
-        for s, ((mel, sc, k), (mel1, sc1, k1)) in enumerate(zip(out, _plain_free(texts, max_steps, threshold, r))):
+        for s, ((mel, sc, k), (mel1, sc1, k1)) in enumerate(zip(out, _plain_free(texts, max_steps, threshold, r, weights))):
             print(f'group {g} sentence {s}: {k} steps, max |grouped - plain| mel {np.abs(mel[:k] - mel1[:k]).max():.3e} '
                   f'attention {np.abs(sc[:k] - sc1[:k]).max():.3e}')
             assert k == k1, (g, s, k, k1)
@@ -148,12 +148,14 @@ def _seeded_mel(N):
     return (random_mel(500 + N, N) * 8 - 4).astype(np.float32)           # [-4, 4], the decoder's scale
 
 
-def _forced_call(texts, Ns, r):
+def _forced_call(texts, Ns, r, weights='plain', mels=None):
+    """A `wrnn_taco_forced_call` over FILLed buffers and a workspace of its own; the forced mels are `_seeded_mel(N)`, or `mels` ((80, N) each)."""
     from wavernn_amd import _lib
-    L, tts, dev = _lib.lib(), _tts(r), torch.device('cuda', 0)
+    L, tts, dev = _lib.lib(), _tts(r, weights), torch.device('cuda', 0)
     S = len(texts)
-    encs = [_enc(t, r) for t in texts]
-    force = [torch.from_numpy(_seeded_mel(N)).to(dev) for N in Ns]
+    encs = [_enc(t, r, weights) for t in texts]
+    force = [torch.from_numpy(np.ascontiguousarray(m, np.float32)).to(dev) for m in (mels or [_seeded_mel(N) for N in Ns])]
+    assert [f.shape for f in force] == [(80, N) for N in Ns]
     steps = [(N + r - 1) // r for N in Ns]
     outs = [torch.full((k + PAD, 80, r), FILL, device=dev) for k in steps]
     scores = [torch.full((k + PAD, e[0].size(0)), FILL, device=dev) for k, e in zip(steps, encs)]

@@ -41,13 +41,13 @@ def _seeded_mel(N):
     return (random_mel(500 + N, N) * 8 - 4).astype(np.float32)
 
 
-def _forced(texts, mels, r=1):
+def _forced(texts, mels, r=1, weights='plain'):
     """`wrnn_taco_decode_forced` into FILLed buffers of steps_s + PAD rows: [(mel (80, steps_s r), attention (steps_s, n_s))] per sentence.  The
     status words must read clean and the PAD rows must still hold FILL."""
     from wavernn_amd import _lib
-    L, tts, dev = _lib.lib(), _tts(r), torch.device('cuda', 0)
+    L, tts, dev = _lib.lib(), _tts(r, weights), torch.device('cuda', 0)
     S = len(texts)
-    encs = [_enc(t, r) for t in texts]
+    encs = [_enc(t, r, weights) for t in texts]
     force = [torch.from_numpy(np.ascontiguousarray(m, np.float32)).to(dev) for m in mels]
     steps = [(m.shape[1] + r - 1) // r for m in mels]
     outs = [torch.full((k + PAD, 80, r), FILL, device=dev) for k in steps]

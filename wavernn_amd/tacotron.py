@@ -647,7 +647,8 @@ class TacotronInference:
         reads column k r - 1 of `m` (n_mels, N), the <GO> frame at k = 0; ceil(N / r) steps, no stop test.  Returns (mel (1, n_mels, steps r),
         attention (steps, n)) device tensors."""
         dev, n = self.device, seq.size(1)
-        z = lambda *s: torch.zeros(*s, device=dev)
+        m = m.to(seq.dtype)
+        z = lambda *s: torch.zeros(*s, device=dev, dtype=seq.dtype)            # (a float64 state dict decodes in float64)
         st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
                   c2=z(1, self.lstm_dims), context=z(1, self.decoder_dims), cumulative=z(1, n), attention=z(1, n))
         frames, scores = [], []
@@ -759,7 +760,7 @@ class TacotronInference:
             frames = [mel]
         else:
             n = seq.size(1)
-            z = lambda *s: torch.zeros(*s, device=dev)
+            z = lambda *s: torch.zeros(*s, device=dev, dtype=seq.dtype)        # (a float64 state dict decodes in float64)
             st = dict(attn_h=z(1, self.decoder_dims), h1=z(1, self.lstm_dims), h2=z(1, self.lstm_dims), c1=z(1, self.lstm_dims),
                       c2=z(1, self.lstm_dims), context=z(1, self.decoder_dims), cumulative=z(1, n), attention=z(1, n))
             prenet_in = z(1, self.n_mels)                                          # the <GO> frame
