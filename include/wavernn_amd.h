@@ -73,7 +73,13 @@ enum {
                                noise_lib, progress, timer and info as on wrnn_generic_kernel.  THE LDS RULE: the activations of the 16 segments live in LDS,
                                16 * 4 * (up4(1 + feat + aux) + 2 * up4(max(rnn, fc) + aux) + 2 * up4(rnn)) + 2560 bytes (up4: rounded up to a multiple of 4),
                                and must fit one CU's 160 KiB = 163840 (rnn = fc = 512, feat 80, aux 32: 145152; rnn = fc = 576 still fits, 640 does not); RAW: <= 2048
-                               classes.  Other dims: WRNN_ERR_ARG with the bytes needed -- stay on `auto` */
+                               classes.  Other dims: WRNN_ERR_ARG with the bytes needed -- stay on `auto`.
+                               THE WIDE FORM (csrc/wrnn_tile_wide.hip, wrnn_tile_wide_kernel): wrnn_options.clusters = 2, 4 or 8 spreads the rows of every
+                               matrix stage of a tile over that many workgroups, which hand the stage's output to one another through the workspace (one
+                               all-gather per stage); the samples and logits are wrnn_tile_kernel's bit for bit.  ONE round: ceil(n_segments / 16) * clusters
+                               workgroups, at most one per CU, launched cooperatively -- more segments than that: WRNN_ERR_ARG (the text names the largest
+                               count), a refused launch: WRNN_ERR_RESIDENCY; plain tile runs either call.  Every refusal and option of tile applies; the
+                               workspace grows by the hand-off buffers (by tiles and dims, not by T); a kernel that gives up waiting: wrnn_status() */
     WRNN_ALGO_TILE_SPARSE = 12, /* WRNN_ALGO_TILE for a PRUNED model of non-shipped dims (csrc/wrnn_tile_sparse.hip, wrnn_tile_sparse_kernel; on request only): the
                                same dataflow, LDS rule, workspace and options, but the four GRU matrices -- and fc1 / fc2 -- run as gathered block-sparse MFMA
                                stages over the pack's TILE-SPARSE VIEW, so the pruned 16x1 blocks are neither streamed nor multiplied.  wrnn_pack_create builds
@@ -154,9 +160,11 @@ typedef struct wrnn_timer wrnn_timer;
 
 /* What a wrnn_generate* call decided (filled synchronously, before the call returns). */
 typedef struct wrnn_run_info {
-    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_octo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" / "wrnn_tile_kernel" */
+    const char *kernel;      /* "wrnn_duo_kernel" / "wrnn_octo_kernel" / "wrnn_chain_kernel" / "wrnn_sparse_kernel" / "wrnn_loop_kernel" / "wrnn_stream_kernel" / "wrnn_generic_kernel" / "wrnn_tile_kernel" /
+                                "wrnn_tile_sparse_kernel" / "wrnn_tile_bf16_kernel" / "wrnn_tile_wide_kernel" */
     int32_t units_per_wg;    /* hidden units per workgroup (16; sparse: 64; stream: 0) */
-    int32_t clusters;        /* independent CU clusters, each holding one copy of the weights */
+    int32_t clusters;        /* independent CU clusters, each holding one copy of the weights; wrnn_tile_wide_kernel: workgroups per tile of 16 segments (2, 4, 8),
+                                with units_per_wg = 16, depth = 0, rounds = 1, launches = 1, slab_steps = T */
     int32_t depth;           /* groups of <= 16 segments in flight per cluster */
     int32_t rounds;          /* rounds of clusters x depth groups the segments were cut into */
     int32_t slab_steps;      /* steps per launch of a persistent kernel = one conditioning slab (wrnn_loop_kernel: steps of hoisted cI
@@ -173,7 +181,8 @@ typedef struct wrnn_options {
     int32_t struct_bytes;
     int32_t algo;            /* WRNN_ALGO_*                                                                  (default AUTO) */
     int32_t depth;           /* groups in flight per cluster, 1..8 (sparse: does not apply -- see sparse_groups); 0 = the library picks */
-    int32_t clusters;        /* loop kernel: clusters to use (1, 2 or 4); 0 = the library picks */
+    int32_t clusters;        /* loop kernel: clusters to use (1, 2 or 4); 0 = the library picks.  WRNN_ALGO_TILE: workgroups per tile -- 0 or 1 = wrnn_tile_kernel,
+                                2, 4, 8 = wrnn_tile_wide_kernel, anything else WRNN_ERR_ARG; WRNN_ALGO_TILE_SPARSE / _TILE_BF16: a value above 1 is WRNN_ERR_ARG */
     int32_t cond_valu;       /* stream kernel: 1 = hoisted conditioning on VALU instead of MFMA (cross-check) */
     int32_t slab_steps;      /* loop kernel: conditioning slab length in steps; 0 = sized to ~96 MB */
     int32_t t_begin, t_end;  /* run steps [t_begin, t_end) of the T; 0,0 = all.  t_begin > 0 CONTINUES the call that ended at

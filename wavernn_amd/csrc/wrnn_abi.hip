@@ -32,6 +32,9 @@ bool generic_dims_ok(int H, int F, int M, int A, int C, int mode);
 hipError_t launch_tile(const GenArgs &args, int mode, hipStream_t stream);
 size_t tile_lds_bytes(int H, int F, int M, int A, int C);
 bool tile_dims_ok(int H, int F, int M, int A, int C, int mode);
+hipError_t launch_tile_wide(const GenArgs &args, int mode, int W, void *xws, unsigned *status, hipStream_t stream);
+size_t tile_wide_flag_bytes(int tiles);
+size_t tile_wide_xbuf_bytes(int tiles, int H, int F, int C, int mode);
 hipError_t launch_tile_sparse(const GenArgs &args, const TileSparseArgs &sp, int mode, bool fcs, hipStream_t stream);
 hipError_t launch_tile_bf16(const GenArgs &args, const TileBf16Args &bw, int mode, hipStream_t stream);
 hipError_t launch_duo(const LoopArgs &args, int ncl, int mode, hipStream_t stream);
@@ -601,7 +604,7 @@ int enqueue_progress(const wrnn_options *o, int done, int T, int n, hipStream_t 
     return WRNN_OK;
 }
 
-enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, K_TILE_SPARSE, K_TILE_BF16, N_KINDS };
+enum Kind { K_STREAM, K_GENERIC, K_LOOP, K_DUO, K_OCTO, K_CHAIN, K_SPARSE, K_TILE, K_TILE_SPARSE, K_TILE_BF16, K_TILE_WIDE, N_KINDS };
 constexpr int DUO_TAB_FPS = 8;       // rows per segment of the per-slab aux tables: a slab covers at most (DUO_TAB_FPS - 2) hops + 1 steps
 constexpr bool DUO_AUTO = true;      // `auto` runs MoL on wrnn_duo_kernel at every depth (round 4, profiles/r04a_probe_new.json: 13.5 vs 16.6 us per step
                                      // with one group in flight, 17.9 vs 21.7 with two, 26.2 vs 36 with four; round 3's kernel paid off from depth 3 on)
@@ -652,6 +655,8 @@ const KindDesc KINDS[N_KINDS] = {
     /* K_TILE_SPARSE */ {"wrnn_tile_sparse_kernel", 16, 0, false, false, false},
     // (wrnn_tile_kernel with the eight matrices in bfloat16, on the bf16 MFMA; on request)
     /* K_TILE_BF16 */ {"wrnn_tile_bf16_kernel", 16, 0, false, false, false},
+    // (wrnn_tile_kernel with the rows of every stage spread over wrnn_options.clusters = 2, 4 or 8 workgroups per tile; on request)
+    /* K_TILE_WIDE */ {"wrnn_tile_wide_kernel", 16, 0, false, false, false},
 };
 
 // what a call will run: kernel, split, rounds, slab length
@@ -667,6 +672,7 @@ struct WsLayout {
     size_t cI, npre;                    // stream kernel: whole-T conditioning; persistent kernels: one slab of derived MOL noise
     size_t nlib;                        // wrnn_options.noise_lib: the noise the library draws, in the layout of `noise` -- one slab (persistent kernels) or all T steps
     size_t xbuf, state, cIf;            // loop kernel: exchange buffer, per-round state, conditioning slab
+    size_t wide;                        // wrnn_tile_wide_kernel: flag block | per-(tile, stage) hand-off buffers
     size_t total;
 };
 size_t al(size_t x) { return (x + 255) / 256 * 256; }
@@ -760,25 +766,46 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
     const int groups = (B + SEG - 1) / SEG;
     pl->kind = K_STREAM; pl->ncl = 0; pl->G = 0; pl->rounds = 1; pl->per_round = B; pl->slab = T; pl->ngr_max = groups;
     if (algo == WRNN_ALGO_TILE) {       // on request only: wrnn_generic_kernel's dataflow for 16 segments per workgroup (csrc/wrnn_tile.hip)
+        // wrnn_options.clusters = 2, 4, 8: the rows of every stage on that many workgroups per tile (csrc/wrnn_tile_wide.hip); 0, 1: wrnn_tile_kernel
+        const int width = o->clusters;
+        if (width != 0 && width != 1 && width != 2 && width != 4 && width != 8) {
+            set_err("wrnn_options.clusters = %d under algo tile: 0 or 1 (wrnn_tile_kernel, one workgroup per tile) or 2, 4, 8 (wrnn_tile_wide_kernel: that many "
+                    "workgroups per tile)", width);
+            return WRNN_ERR_ARG;
+        }
+        const bool wide = width > 1;
+        const char *const kn = wide ? "wrnn_tile_wide_kernel" : "wrnn_tile_kernel";
         if (!p->generic) {
-            set_err("wrnn_tile_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo auto "
-                    "picks its kernel", H);
+            set_err("%s runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo auto "
+                    "picks its kernel", kn, H);
             return WRNN_ERR_ARG;
         }
         if (!tile_dims_ok(p->gH, p->gF, p->gM, p->gA, p->C, p->mode)) {
-            set_err("wrnn_tile_kernel: rnn %d, fc %d, feat %d, aux %d, %d classes need %zu bytes of LDS per workgroup, the limit is %d (and RAW: <= 2048 classes); "
-                    "algo auto runs this pack on wrnn_generic_kernel", p->gH, p->gF, p->gM, p->gA, p->C, tile_lds_bytes(p->gH, p->gF, p->gM, p->gA, p->C), 160 * 1024);
+            set_err("%s: rnn %d, fc %d, feat %d, aux %d, %d classes need %zu bytes of LDS per workgroup, the limit is %d (and RAW: <= 2048 classes); "
+                    "algo auto runs this pack on wrnn_generic_kernel", kn, p->gH, p->gF, p->gM, p->gA, p->C, tile_lds_bytes(p->gH, p->gF, p->gM, p->gA, p->C), 160 * 1024);
             return WRNN_ERR_ARG;
         }
         if (partial) { set_err("a partial step range needs a persistent loop kernel"); return WRNN_ERR_ARG; }
-        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on wrnn_tile_kernel)"); return WRNN_ERR_ARG; }
-        pl->kind = K_TILE;
+        if (two_groups) { set_err("wrnn_options.sparse_groups = 2: only wrnn_sparse_kernel runs two groups per cluster (this call runs on %s)", kn); return WRNN_ERR_ARG; }
+        if (wide && (long)groups * width > p->n_cus) {
+            // ONE round, the W members of every tile co-resident: a workgroup holds a CU's LDS
+            set_err("wrnn_tile_wide_kernel: %d segments are %d tiles of 16, and %d workgroups per tile need %ld CUs; this device has %d: width %d takes at most %d "
+                    "segments here -- plain algo tile (wrnn_options.clusters = 0) runs this call", B, groups, width, (long)groups * width, p->n_cus, width,
+                    p->n_cus / width * SEG);
+            return WRNN_ERR_ARG;
+        }
+        pl->kind = wide ? K_TILE_WIDE : K_TILE;
+        if (wide) pl->ncl = width;
         return WRNN_OK;
     }
     if (algo == WRNN_ALGO_TILE_SPARSE) {        // on request only: wrnn_tile_kernel on the pack's tile-sparse view (csrc/wrnn_tile_sparse.hip)
         if (!p->generic) {
             set_err("wrnn_tile_sparse_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo "
                     "auto picks its kernel, wrnn_sparse_kernel for a block-sparse one", H);
+            return WRNN_ERR_ARG;
+        }
+        if (o->clusters > 1) {
+            set_err("wrnn_options.clusters = %d under algo tile_sparse: only the float32 tile kernel (algo tile) has the wide form", o->clusters);
             return WRNN_ERR_ARG;
         }
         if (p->sp_nbp <= 0) {
@@ -806,6 +833,10 @@ int make_plan(const wrnn_plan_traits *p, int B, int T, const wrnn_options *o, Pl
         if (!p->generic) {
             set_err("wrnn_tile_bf16_kernel runs generic packs only (non-shipped dims, or RAW with more than %d classes): this pack has the shipped dims -- algo auto "
                     "picks its kernel", H);
+            return WRNN_ERR_ARG;
+        }
+        if (o->clusters > 1) {
+            set_err("wrnn_options.clusters = %d under algo tile_bf16: only the float32 tile kernel (algo tile) has the wide form", o->clusters);
             return WRNN_ERR_ARG;
         }
         if (!tile_dims_ok(p->gH, p->gF, p->gM, p->gA, p->C, p->mode)) {
@@ -929,8 +960,10 @@ WsLayout ws_layout(const wrnn_plan_traits *p, const Plan &pl, int B, int T, int 
     l.xcc = o;    o = al(o + XCC_WORDS * sizeof(unsigned));
     l.segs = o;   o = al(o + (size_t)3 * B * sizeof(int));       // positions | limits | mel offsets (wrnn_options.mel_stage)
     l.melc = o;   o = al(o + (size_t)3 * LAST_SCALE * sizeof(float));
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16 || pl.kind == K_TILE_WIDE) {
         l.nlib = o; if (noise_lib) o = al(o + (size_t)T * noise_row);
+        l.wide = o;         // (behind everything wrnn_tile_kernel's workspace holds; by the tile count and the dims, not by T)
+        if (pl.kind == K_TILE_WIDE) o = al(o + tile_wide_flag_bytes(pl.ngr_max) + tile_wide_xbuf_bytes(pl.ngr_max, p->gH, p->gF, p->C, p->mode));
         l.total = o;
         return l;
     }
@@ -1103,7 +1136,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         HIPCHK(hipMemcpyAsync(ws + l.segs + (size_t)2 * B * sizeof(int), o->seg_moff, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
         HIPCHK(launch_put_floats((float *)(ws + l.melc), coef, 3 * LAST_SCALE, stream));       // (by value, as kernel arguments: `coef` is a stack array)
     }
-    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16) {
+    if (pl.kind == K_GENERIC || pl.kind == K_TILE || pl.kind == K_TILE_SPARSE || pl.kind == K_TILE_BF16 || pl.kind == K_TILE_WIDE) {
         GenArgs g;
         memset(&g, 0, sizeof g);
         g.I_T = p->g_I_T; g.I_b = p->I_b; g.w_ih1T = p->w_ih1T; g.w_hh1T = p->w_hh1T; g.b_ih1 = p->b_ih1; g.b_hh1 = p->b_hh1;
@@ -1119,6 +1152,15 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         if (pl.kind == K_TILE_SPARSE && !p->ts_view) { set_err("this pack has no tile-sparse view"); return WRNN_ERR_ARG; }      // (the planner's traits are the pack's own: never)
         if (pl.kind == K_TILE_BF16 && !p->bf_bytes) { set_err("this pack has no bf16 view"); return WRNN_ERR_ARG; }             // (likewise)
+        if (pl.kind == K_TILE_WIDE) {
+            // a cooperative launch: W members per tile that cannot be co-resident are refused here, not hung
+            const hipError_t e = launch_tile_wide(g, p->tr.mode, pl.ncl, ws + l.wide, (unsigned *)(ws + l.status), stream);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                set_err("%s cooperative launch failed: %s", k.name, hipGetErrorString(e));
+                return e == hipErrorCooperativeLaunchTooLarge ? WRNN_ERR_RESIDENCY : WRNN_ERR_HIP;
+            }
+        } else
         HIPCHK(pl.kind == K_TILE_BF16   ? launch_tile_bf16(g, p->bf, p->tr.mode, stream)
                : pl.kind == K_TILE_SPARSE ? launch_tile_sparse(g, p->ts, p->tr.mode, p->ts_view == 2, stream)
                : pl.kind == K_TILE      ? launch_tile(g, p->tr.mode, stream)
@@ -1127,6 +1169,7 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
         wrnn_run_info gi;
         memset(&gi, 0, sizeof gi);
         gi.kernel = k.name; gi.rounds = 1; gi.slab_steps = T; gi.launches = 1;
+        if (pl.kind == K_TILE_WIDE) { gi.units_per_wg = k.units_per_wg; gi.clusters = pl.ncl; }
         if (o->info) *o->info = gi;
         return enqueue_progress(o, T, T, B, stream);
     }

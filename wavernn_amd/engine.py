@@ -101,6 +101,11 @@ class LoopEngine:
         self._launches = 0
         self._slice_algo = None
         self._auto_floor = None           # the kernel an `auto` call degraded to after a refused cooperative launch: where later `auto` calls start
+        #: workgroups per tile (2, 4, 8) of an algo='tile' call that names no `clusters` itself: wrnn_tile_wide_kernel (`WaveRNN.tile_width` sets it).  A call
+        #: with more segments than the width takes on this device, or whose cooperative launch is refused, runs on plain wrnn_tile_kernel: one warning
+        self.tile_width = 0
+        self._tile_narrow = False         # a wide launch was refused (not co-resident): later calls stay on wrnn_tile_kernel
+        self._tile_warned = False
         self._progress_keep = []          # ctypes thunks of progress callbacks whose host functions may still be queued on the stream
 
     def __del__(self):
@@ -161,14 +166,34 @@ class LoopEngine:
             o.t_begin, o.t_end = int(t_range[0]), int(t_range[1])
         return o
 
+    def _tile_clusters(self, algo, clusters, n_segments, T):
+        """`clusters` of a call: under algo='tile' with none named, `self.tile_width` where the planner takes this many segments at that width."""
+        if algo != 'tile' or clusters or self.tile_width <= 1 or self._tile_narrow:
+            return clusters
+        o, i = self.options('tile', clusters=self.tile_width), _lib.RunInfo()
+        rc = self.lib.wrnn_plan_segments(self._pack, n_segments, T, ctypes.byref(o), ctypes.byref(i))
+        why = self.lib.wrnn_last_error().decode()
+        if rc == _lib.ERR_ARG and 'takes at most' in why:       # too many segments for this width: the planner's own answer names plain tile
+            self._warn_tile(why)
+            return 0
+        return self.tile_width                                  # (any other refusal is the call's own to raise)
+
+    def _warn_tile(self, why):
+        if not self._tile_warned:
+            import warnings
+            warnings.warn('wavernn_amd: ' + why + '; running on wrnn_tile_kernel (tile_width ignored for such calls)')
+            self._tile_warned = True
+
     def plan(self, n_segments, T, **kw):
         """What a run over this many segments would launch (`wrnn_plan_segments`): dict(kernel, clusters, depth, rounds, ...)."""
+        kw['clusters'] = self._tile_clusters(kw.get('algo', 'auto'), kw.get('clusters', 0), n_segments, T)
         o, i = self.options(**kw), _lib.RunInfo()
         _lib.check(self.lib.wrnn_plan_segments(self._pack, n_segments, T, ctypes.byref(o), ctypes.byref(i)), 'wrnn_plan_segments')
         return dict(kernel=(i.kernel or b'').decode(), units_per_wg=int(i.units_per_wg), clusters=int(i.clusters), depth=int(i.depth),
                     rounds=int(i.rounds), slab_steps=int(i.slab_steps))
 
     def workspace_bytes(self, n_segments, T, n_frames, **kw):
+        kw['clusters'] = self._tile_clusters(kw.get('algo', 'auto'), kw.get('clusters', 0), n_segments, T)
         o = self.options(**kw)
         return int(self.lib.wrnn_workspace_bytes_segments(self._pack, n_segments, T, n_frames, ctypes.byref(o)))
 
@@ -181,7 +206,8 @@ class LoopEngine:
         Enqueues on the current stream; `check=True` synchronises and raises if a kernel gave up.
 
         depth / clusters / slab_steps / cond_valu / sparse_groups: `wrnn_options` (0 = the library picks; sparse_groups=2: two groups per
-        cluster of wrnn_sparse_kernel, same samples).  t_range=(t0, t1) runs only those
+        cluster of wrnn_sparse_kernel, same samples; algo='tile': clusters = 2, 4, 8 runs wrnn_tile_wide_kernel, that many workgroups per tile of 16
+        segments, same samples -- none named: `self.tile_width`).  t_range=(t0, t1) runs only those
         steps; t0 > 0 continues the previous call on this engine's workspace (pass the same `out`; `noise` then holds the
         rows of [t0, t1) only) -- how long RAW runs draw their noise in chunks instead of T*B*C floats at once.
         progress: optional `f(steps_done, T, n_segments)` called from a HIP runtime thread when the device has finished each
@@ -213,6 +239,8 @@ class LoopEngine:
         if not lib_noise and noise.numel() != need:
             raise ValueError(f'noise has {noise.numel()} elements, expected {need}')
         n_frames = int(aux.shape[0])
+        named_clusters = clusters
+        clusters = self._tile_clusters(algo, clusters, B, T)
         o = self.options(algo, depth, clusters, slab_steps, cond_valu, t_range, tuning, sparse_groups, lib_noise)
         if lib_noise:                     # (the id array is a host array read during the call only)
             o.noise_seed = int(noise_seed) & (2 ** 64 - 1)
@@ -255,6 +283,15 @@ class LoopEngine:
         rc = self.lib.wrnn_generate_segments(self._pack, B, T, seg_pos.ctypes.data, seg_lim.ctypes.data, L, hop, n_frames,
                                              mels_up.data_ptr(), aux.data_ptr(), None if lib_noise else noise.data_ptr(), out.data_ptr(),
                                              self._ws.data_ptr(), self._ws.numel(), ctypes.byref(o), stream)
+        if rc == _lib.ERR_RESIDENCY and algo == 'tile' and clusters > 1 and not named_clusters:
+            # the W workgroups of a tile are not co-resident right now: plain wrnn_tile_kernel needs no residency (the same samples), from now on
+            self._warn_tile('cooperative launch refused (' + self.lib.wrnn_last_error().decode() + ')')
+            self._tile_narrow = True
+            if progress is not None:
+                self._progress_keep.pop()
+            return self.run_segments(mels_up if rows_in is None else rows_in, aux, seg_pos, seg_lim, T, noise, hop, algo=algo, force_x=force_x,
+                                     want_logits=want_logits, check=check, slab_steps=slab_steps, cond_valu=cond_valu, t_range=t_range, out=out, logits=logits,
+                                     phase_clocks=phase_clocks, tuning=tuning, progress=progress, noise_seed=noise_seed, noise_seg_id=noise_seg_id)
         if rc == _lib.ERR_RESIDENCY and t0 == 0 and (algo == 'auto' or _fallback):
             # the persistent grid is not co-resident right now (CU masking, a smaller partition, another cooperative kernel).  `auto`
             # degrades step by step (FALLBACK_ALGO): wrnn_sparse_kernel -> two workgroups per CU (wrnn_duo_kernel) -> one (wrnn_loop_kernel;

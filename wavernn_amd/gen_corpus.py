@@ -59,6 +59,8 @@ def main(argv=None):
                     help='where the sampling noise comes from (default: cpu with --seed, else device); cpu and library need --seed')
     ap.add_argument('--sparse-groups', type=int, default=None, choices=[1, 2],
                     help='a pruned MoL model on wrnn_sparse_kernel: groups of segments per cluster (2: 512 segments a round; a dense model ignores it)')
+    ap.add_argument('--tile-width', type=int, default=0, choices=[0, 2, 4, 8], help="with --algo tile: workgroups per tile of 16 segments "
+                        "(model.tile_width; wrnn_tile_wide_kernel, the same samples bit for bit).  0 (default): wrnn_tile_kernel.  Any other --algo refuses it")
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
                          "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
@@ -93,6 +95,7 @@ def main(argv=None):
         model.load(a.weights)
     model.sparse_groups = a.sparse_groups
     model.loop_algo = a.algo
+    model.tile_width = a.tile_width
     paths, mels = load_mels(a.mels)
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
     noise = a.noise or ('cpu' if seeds is not None else 'device')

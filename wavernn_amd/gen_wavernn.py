@@ -70,6 +70,8 @@ def main(argv=None):
     ap.add_argument('--noise', choices=['cpu', 'device', 'library'], default=None,
                     help="cpu (default): the reference's CPU stream after torch.manual_seed(--seed); device: torch's device generator; library: drawn inside "
                          'the loop from a counter-based generator -- the utterance sounds the same alone and in any gen_corpus batch with the same seed')
+    ap.add_argument('--tile-width', type=int, default=0, choices=[0, 2, 4, 8], help="with --algo tile: workgroups per tile of 16 segments "
+                        "(model.tile_width; wrnn_tile_wide_kernel, the same samples bit for bit).  0 (default): wrnn_tile_kernel.  Any other --algo refuses it")
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS),
                     help="the loop kernel (model.loop_algo; WRNN_ALGO_* of include/wavernn_amd.h).  auto (default): the library picks; a kernel by name runs or "
                          "says what it needs -- 'tile' takes models with other dims than the shipped ones, 16 segments per workgroup; 'tile_sparse' is 'tile' for a PRUNED "
@@ -92,6 +94,7 @@ def main(argv=None):
         ap.error('--device-noise contradicts --noise ' + a.noise)
     model.noise_source = 'device' if a.device_noise else (a.noise or 'cpu')
     model.loop_algo = a.algo
+    model.tile_width = a.tile_width
     if a.seed is not None:
         torch.manual_seed(a.seed)
         model.noise_seed = a.seed

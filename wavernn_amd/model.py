@@ -141,6 +141,10 @@ class WaveRNN(nn.Module):
         #: wrnn_tile_kernel (16 segments per workgroup) instead of `auto`'s wrnn_generic_kernel (one); 'tile_bf16': the same with the eight loop matrices rounded to
         #: bfloat16 (wrnn_tile_bf16_kernel: NOT the reference's arithmetic -- `synthetic.bf16_round_state_dict` gives the model it runs)
         self.loop_algo = 'auto'
+        #: loop_algo == 'tile': 2, 4 or 8 = the rows of every stage of a tile of 16 segments on that many workgroups (wrnn_tile_wide_kernel: wrnn_options.clusters
+        #: under WRNN_ALGO_TILE; the same samples bit for bit).  0 (default) = wrnn_tile_kernel.  A call with more segments than the width takes on this
+        #: device, or whose cooperative launch is refused, runs on wrnn_tile_kernel (one warning).  Any other loop_algo: ValueError -- never dropped silently
+        self.tile_width = 0
         #: 2 = a run planned on wrnn_sparse_kernel puts TWO groups of <= 16 segments on each of its 16 clusters (wrnn_options.sparse_groups: 512 segments a
         #: round instead of 256, the same samples; MoL models whose Linear layers are pruned too).  None (default) = one group.  A run on any other
         #: kernel -- a dense model, or the next kernel after a refused cooperative launch -- ignores it.
@@ -234,6 +238,11 @@ class WaveRNN(nn.Module):
             dev = next(self.parameters()).device
             self._engine = LoopEngine(sd, self.mode, device=dev)
             self._engine_key = key
+        width = int(self.tile_width or 0)
+        if width > 1 and self.loop_algo != 'tile':
+            raise ValueError(f"tile_width = {width} needs loop_algo == 'tile': only wrnn_tile_kernel has the wide form (wrnn_tile_wide_kernel), and "
+                             f"loop_algo is {self.loop_algo!r}; set tile_width = 0 or loop_algo = 'tile'")
+        self._engine.tile_width = width
         return self._engine
 
     def _pre_engine(self):

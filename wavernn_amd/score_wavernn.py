@@ -38,6 +38,8 @@ def main(argv=None):
     ap.add_argument('--wavs', required=True, help='directory of <id>.npy or <id>.wav audio at the model sample rate')
     ap.add_argument('--mode', default='MOL', choices=['MOL', 'RAW'])
     ap.add_argument('--mu_law', action='store_true', help='RAW: mu-law encode the waveform (hparams.mu_law) instead of linear labels')
+    ap.add_argument('--tile-width', type=int, default=0, choices=[0, 2, 4, 8], help="with --algo tile: workgroups per tile of 16 segments "
+                        "(model.tile_width; wrnn_tile_wide_kernel, the same samples bit for bit).  0 (default): wrnn_tile_kernel.  Any other --algo refuses it")
     ap.add_argument('--algo', default='auto', choices=sorted(ALGOS), help="the loop kernel (model.loop_algo); 'tile_sparse' scores a pruned model of other dims than the shipped ones on its surviving 16x1 blocks: "
                          "it needs rnn_dims % 16 == 0 and GRU matrices of which at most 41 % of the blocks survive (sparsity >= 0.6); "
                          "'tile_bf16' scores such a model with its weights rounded to bfloat16: against --algo tile that is what the rounding costs, in bits per sample")
@@ -48,6 +50,7 @@ def main(argv=None):
     if a.weights:
         model.load(a.weights)
     model.loop_algo = a.algo
+    model.tile_width = a.tile_width
     wav_dir, ids, mels, wavs = Path(a.wavs), [], [], []
     for mel_path in sorted(Path(a.mels).glob('*.npy')):
         audio = next((wav_dir / (mel_path.stem + ext) for ext in ('.npy', '.wav') if (wav_dir / (mel_path.stem + ext)).exists()), None)
