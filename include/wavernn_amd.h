@@ -797,6 +797,34 @@ int wrnn_taco_decode_forced_groups(int device, const wrnn_taco_weights *w, const
  * library was built with (0: contiguous halves; 1: interleaved, a group on four XCDs), -1 for a block outside the grid or a NULL output. */
 int wrnn_debug_taco_group_of(int32_t block, int32_t *group, int32_t *local);
 
+/*
+ * A WATCHED call (appended to ABI v9: the symbols tell whether a library has them): wrnn_generate_segments on one of the kernels that are launched once
+ * for all T steps -- wrnn_generic_kernel, wrnn_tile_kernel, wrnn_tile_sparse_kernel, wrnn_tile_bf16_kernel, wrnn_tile_wide_kernel -- which also publishes
+ * how far it has got, so that finished audio can be handed on while it runs.  Arguments, behaviour and samples are those of wrnn_generate_segments;
+ * besides, the call zeroes progress[0 .. W) on the stream in front of the launch (W = wrnn_watch_words), and every workgroup that writes `out` stores
+ * t + 1 into ITS word after step t whenever (t + 1) % progress_every == 0 or t + 1 == T.  A word's value v says: steps [0, v) of that workgroup's rows of
+ * `out` are complete and visible to a kernel or copy launched from now on (wrnn_generic_kernel: word b = segment b; the tile kernels: word g = segments
+ * [16 g, 16 g + 16)).  So min over the W words = the columns of ALL of `out` that are final.  Readers are launched LATER, on another stream: copy the words
+ * to the host, take the minimum m, then launch whatever reads out[:, :m] (wrnn_post_chunk, a copy).  Nothing may poll the words from inside a kernel, and
+ * the loop kernel never reads them or waits for anybody: a caller that stops looking changes nothing.  Publishing costs an L2 write-back (microseconds):
+ * progress_every = 64 keeps it far below a percent of these kernels' step times.  The words before the call are NOT zero until the stream reaches the
+ * call's memset: order the first look behind an event recorded in front of the call, on words the caller has zeroed.
+ * WRNN_ERR_ARG, before anything is queued, the message naming the cause and the kernel planned: a call that plans onto another kernel (the resumable
+ * kernels -- wrnn_loop / _duo / _sparse / _chain_kernel -- stream through wrnn_options.t_begin / t_end instead; wrnn_stream_kernel does not stream), a NULL
+ * `progress`, progress_every < 1, progress_words < W, a partial step range in `opt`.
+ * wrnn_watch_words: W for such a call, with the same refusals of kernel and step range; no device is touched.
+ */
+int wrnn_generate_segments_watched(const wrnn_pack *p, int32_t n_segments, int32_t T, const int32_t *seg_pos,
+                                   const int32_t *seg_lim, int32_t L, int32_t hop, int32_t n_frames,
+                                   const float *mels_up, const float *aux, const float *noise, float *out,
+                                   void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream,
+                                   unsigned *progress, int32_t progress_words, int32_t progress_every);
+int wrnn_watch_words(const wrnn_pack *p, int32_t n_segments, int32_t T, const wrnn_options *opt, int32_t *words);
+/* Test hook: every refusal of a watched call for a pack with these traits (wrnn_debug_plan's), with neither a pack nor a device.  have_progress: > 0 a
+ * non-NULL `progress`, 0 a NULL one, < 0: answer as wrnn_watch_words (progress_words / progress_every are not looked at).  `words` (may be NULL) <- W. */
+int wrnn_debug_watch(const wrnn_plan_traits *traits, int32_t n_segments, int32_t T, const wrnn_options *opt, int32_t have_progress,
+                     int32_t progress_words, int32_t progress_every, int32_t *words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,8 @@ EXPORTS = ['wrnn_last_error', 'wrnn_abi_version', 'wrnn_device_cus', 'wrnn_pack_
            'wrnn_taco_encode', 'wrnn_taco_postnet', 'wrnn_taco_batch_workspace_bytes', 'wrnn_taco_decode_batch',
            'wrnn_bigru_many', 'wrnn_taco_front_workspace_bytes_many', 'wrnn_taco_encode_many', 'wrnn_taco_postnet_many',
            'wrnn_taco_front_debug_host_handle', 'wrnn_taco_forced_workspace_bytes', 'wrnn_taco_decode_forced',
-           'wrnn_taco_decode_batch_groups', 'wrnn_taco_decode_forced_groups', 'wrnn_debug_taco_group_of']
+           'wrnn_taco_decode_batch_groups', 'wrnn_taco_decode_forced_groups', 'wrnn_debug_taco_group_of',
+           'wrnn_generate_segments_watched', 'wrnn_watch_words', 'wrnn_debug_watch']
 
 
 class Weights(ctypes.Structure):
@@ -260,6 +261,10 @@ def lib():
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.POINTER(Options), ctypes.c_void_p]
+    L.wrnn_generate_segments_watched.argtypes = L.wrnn_generate_segments.argtypes + [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+    L.wrnn_watch_words.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Options), ctypes.POINTER(ctypes.c_int32)]
+    L.wrnn_debug_watch.argtypes = [ctypes.POINTER(PlanTraits), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Options), ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
     L.wrnn_noise_fill.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.wrnn_noise_fill_host.argtypes = L.wrnn_noise_fill.argtypes[:8]
@@ -429,3 +434,13 @@ def tile_bf16_pack_host(W):
     out = np.full(n, 0xFFFF, np.uint16)
     check(min(0, lib().wrnn_debug_tile_bf16_pack(W.ctypes.data, rows, K, out.ctypes.data, n)), 'wrnn_debug_tile_bf16_pack')
     return out.reshape(-1, 4, 8)
+
+
+def watch_words_host(traits, n_segments, T, opts=None, progress=None, progress_words=0, progress_every=1):
+    """`wrnn_debug_watch`: what a watched call (`wrnn_generate_segments_watched`) answers for a pack with these `PlanTraits` -- the words it writes, or
+    WrnnError with the library's refusal.  progress=None: as `wrnn_watch_words` (kernel and step range only); True / False: a non-NULL / NULL `progress`
+    of `progress_words` words, published every `progress_every` steps.  No HIP device is needed."""
+    words = ctypes.c_int32(-1)
+    check(lib().wrnn_debug_watch(ctypes.byref(traits), int(n_segments), int(T), None if opts is None else ctypes.byref(opts),
+                                 -1 if progress is None else int(bool(progress)), int(progress_words), int(progress_every), ctypes.byref(words)), 'wrnn_debug_watch')
+    return int(words.value)

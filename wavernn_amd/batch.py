@@ -510,20 +510,31 @@ def _cut(t0, t1, bound):
     return [(a, min(t1, a + size)) for a in range(t0, t1, size)]
 
 
+def live_release(slices, done, m):
+    """The scheduling decision of the live path (`generate_unbatched(live=True)`): `slices` are the step ranges [t0, t1) of a call in delivery order, the
+    first `done` of them have been released, and the loop kernel has just been seen to have finished steps [0, m).  Returns the new count: the slices
+    [done, result) are released now, in order.  A slice is released only when m covers it (t1 <= m), never twice and never out of order, whatever the
+    sequence of observations -- repeated, stuck, no multiple of the chunk, or running backwards; m = T releases everything."""
+    k = int(done)
+    while k < len(slices) and slices[k][1] <= m:
+        k += 1
+    return k
+
+
 _WARNED_WHOLE = 'wavernn_amd: chunk_steps asks for step slices, but {} does not continue a call (engine.RESUMABLE_KERNELS): the call runs whole and ' \
                 'every utterance is delivered as one chunk at the end'
 
 
 def unbatched_chunks(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequence[int]] = None, noise_source='library', chunk_steps: Optional[int] = None,
-                     max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None, global_rng=False):
+                     max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None, global_rng=False, live=False):
     """The core of `generate_unbatched` and `WaveRNN.generate_stream`, as a generator of (u, start, samples): utterance u's finished samples
     [start, start + len(samples)), in step order and, within a step slice, in the group's order; `samples` is an array of its own.  While the
     generator is suspended the device goes on with the slice queued behind the one just delivered.  global_rng (one utterance, 'cpu' noise): draw
-    from torch's global generator as `WaveRNN.generate` does, instead of a private generator seeded with seeds[u]."""
+    from torch's global generator as `WaveRNN.generate` does, instead of a private generator seeded with seeds[u].  live: `generate_unbatched`."""
     from .rng import draw_steps, burn_ctor_draws
     from . import _lib
     from . import post as _post
-    from .engine import RESUMABLE_KERNELS
+    from .engine import RESUMABLE_KERNELS, WATCHABLE_KERNELS
     t_call = time.perf_counter()
     if noise_source not in ('cpu', 'device', 'library'):
         raise ValueError(f'unknown noise source {noise_source!r}')
@@ -622,7 +633,8 @@ def unbatched_chunks(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequen
                 resumable = kernel in RESUMABLE_KERNELS
                 groups = model.loop_sparse_groups(eng, n, T) if hasattr(model, 'loop_sparse_groups') else 0
                 sliced = chunk_steps is not None and resumable
-                if chunk_steps is not None and not resumable and not warned:
+                watched = bool(live) and chunk_steps is not None and kernel in WATCHABLE_KERNELS
+                if chunk_steps is not None and not resumable and not watched and not warned:
                     import warnings
                     warnings.warn(_WARNED_WHOLE.format(kernel))
                     warned = True
@@ -638,6 +650,72 @@ def unbatched_chunks(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequen
                     eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(s0, s1), hop, t_range=None if (s0 == 0 and s1 == T) else (s0, s1), **run_kw)
 
                 seed_streams()
+                if watched:
+                    # ---- live: the WHOLE call is queued on the main stream and publishes how far it has got (wrnn_generate_segments_watched); ONE side
+                    #      stream looks at the progress words and finishes and copies out every chunk the kernel has passed (these kernels leave most of
+                    #      the chip idle: wrnn_post_chunk has CUs to run on beside them).  Every reader is launched AFTER the look that released its chunk.
+                    k_steps = min(int(chunk_steps), T)
+                    every = min(64, k_steps)                       # a chunk is late by at most one publication
+                    main = torch.cuda.current_stream(device)
+                    # (a HIGH-PRIORITY stream: the runtime keeps the hardware queues of a priority class apart from the others', so a look never sits
+                    # behind the loop kernel in the main stream's hardware queue -- an ordinary side stream may be given that very queue when the
+                    # process has few of them, and every chunk then arrives at the end)
+                    side = torch.cuda.Stream(device, priority=-1)
+                    t_dtype = torch.float32 if want32 else torch.float64
+                    words = torch.zeros(eng.watch_words(n, T, algo=model.loop_algo), dtype=torch.int32, device=device)
+                    words_pin = torch.zeros(words.numel(), dtype=torch.int32, pin_memory=True)
+                    dev_buf = [torch.empty(n * k_steps, dtype=t_dtype, device=device) for _ in range(2)]
+                    pin_buf = [torch.empty(n * k_steps, dtype=t_dtype, pin_memory=True) for _ in range(2)]
+                    wl_dev = torch.from_numpy(wave_len).to(device)
+                    _post.chunk_tables_on_device(hop, C, mu_law, device)      # (made here, on the main stream, not by the first launch on the side stream)
+                    for d in dev_buf + [out, words, wl_dev]:
+                        d.record_stream(side)                      # (read on the side stream: a generator closed early frees them safely)
+                    zeroed, looked, loop_done = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+                    copy_done = [torch.cuda.Event() for _ in range(2)]
+                    zeroed.record(main)
+                    side.wait_event(zeroed)                        # no look in front of the zeroed words (and the tables)
+                    eng.run_segments(mels_up, aux, seg_pos, seg_lim, T, draw(0, T), hop, watch=(words, every), **run_kw)
+                    loop_done.record(main)
+                    slices = [(a, min(T, a + k_steps)) for a in range(0, T, k_steps)]
+                    done = 0
+                    while done < len(slices):                      # ends with loop_done: the poll is bounded by the kernel itself
+                        if loop_done.query():
+                            m = T
+                        else:
+                            with torch.cuda.stream(side):
+                                words_pin.copy_(words, non_blocking=True)
+                            looked.record(side)
+                            looked.synchronize()
+                            m = int(words_pin.min())
+                        upto = live_release(slices, done, m)
+                        if upto == done:
+                            time.sleep(0.0005)
+                            continue
+                        pending = None
+                        for i in range(done, upto):
+                            b, (t0, t1) = i % 2, slices[i]
+                            d = dev_buf[b][:n * (t1 - t0)]
+                            with torch.cuda.stream(side):
+                                _post.chunk_on_device(out, wl_dev, t0, t1, hop, C, mu_law, out64=None if want32 else d, out32=d if want32 else None,
+                                                      min_wave_len=int(wave_len.min()))
+                                pin_buf[b][:n * (t1 - t0)].copy_(d, non_blocking=True)
+                            copy_done[b].record(side)
+                            n_slices += 1
+                            if pending is not None:                # (slice i is queued: now the host may wait for slice i - 1)
+                                pb, p0, p1 = pending
+                                copy_done[pb].synchronize()
+                                yield from deliver(pin_buf[pb][:n * (p1 - p0)].numpy().reshape(n, p1 - p0), p0, p1)
+                            pending = (b, t0, t1)
+                        pb, p0, p1 = pending                       # nothing else is released yet: the last one goes out at once
+                        copy_done[pb].synchronize()
+                        yield from deliver(pin_buf[pb][:n * (p1 - p0)].numpy().reshape(n, p1 - p0), p0, p1)
+                        done = upto
+                    if check:
+                        eng.status()
+                    side.synchronize()
+                    model.last_loop_ms, model.last_loop_kernel = eng.last_loop_ms(), eng.last_loop_kernel()
+                    loop_ms += model.last_loop_ms
+                    continue
                 if not sliced:
                     try:
                         for s0, s1 in _cut(0, T, bound):
@@ -736,7 +814,7 @@ def unbatched_chunks(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequen
 
 
 def generate_unbatched(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequence[int]] = None, noise_source='library', chunk_steps: Optional[int] = None,
-                       on_chunk=None, max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None):
+                       on_chunk=None, max_utterances: int = 64, dtype=np.float64, loop_fn=None, check=True, timings: Optional[dict] = None, live=False):
     """Generate every utterance of `mels` (each (1, feat, N_u) or (feat, N_u)) UNBATCHED -- no folds, no cross-fade seams: the quality mode of
     `generate(batched=False)` -- as the unfolded segments of one loop call per group, and optionally hand the audio on in step slices while the loop
     goes on.  Returns the list of waveforms (`dtype`, (N_u - 1) * hop samples each) in the caller's order.
@@ -755,6 +833,11 @@ def generate_unbatched(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequ
     chunk_steps=k, on a kernel that continues a call (`engine.RESUMABLE_KERNELS`): the loop runs in slices of k steps; behind every slice one
     `wrnn_post_chunk` launch on the same stream and the chunk's copy into one of two page-locked buffers on a side stream, the next slice queued
     before the host waits for that copy.  Any other kernel runs the call whole and delivers each utterance as one chunk at the end (one warning).
+    live=True with chunk_steps=k, on a kernel that is launched once for all steps (`engine.WATCHABLE_KERNELS`: every model of non-shipped dims): the
+    call is queued whole and publishes its progress every min(64, k) steps (`wrnn_generate_segments_watched`); one side stream looks at the progress
+    words about every 0.5 ms and runs `wrnn_post_chunk` and the chunk's copy for every slice of k steps the kernel has passed, while it goes on --
+    the same chunks, in the same order, with the same bits as the sliced path would deliver.  On a kernel that continues a call `live` changes
+    nothing (the sliced path), nor on wrnn_stream_kernel (whole, with the warning), nor under `loop_fn`.
 
     on_chunk(u, start, samples), on the calling thread, in step order and within a slice in the group's order, for every utterance with
     start < wave_len_u: `samples` (length min(t1, wave_len_u) - start) is a copy the callee may keep.  The returned waveforms are assembled from
@@ -766,7 +849,7 @@ def generate_unbatched(model, mels: Sequence, mu_law: bool, seeds: Optional[Sequ
     and slices (post-loop launches)."""
     parts = [[] for _ in mels]
     for u, start, samples in unbatched_chunks(model, mels, mu_law, seeds=seeds, noise_source=noise_source, chunk_steps=chunk_steps,
-                                              max_utterances=max_utterances, dtype=dtype, loop_fn=loop_fn, check=check, timings=timings):
+                                              max_utterances=max_utterances, dtype=dtype, loop_fn=loop_fn, check=check, timings=timings, live=live):
         assert start == sum(len(p) for p in parts[u])
         if on_chunk is not None:
             on_chunk(u, start, samples)

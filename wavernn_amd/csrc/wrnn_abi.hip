@@ -1047,6 +1047,44 @@ int plan_report(const wrnn_plan_traits *tr, int B, int T, int n_frames, const wr
     if (ws_bytes) *ws_bytes = ws_layout(tr, pl, B, T, n_frames, o.noise_lib != 0).total;
     return WRNN_OK;
 }
+
+// A WATCHED call (wrnn_generate_segments_watched): the one-launch kernels publish how far they have got, one word per workgroup that writes `out`
+// (wrnn_generic_kernel: one per segment; the tile kernels: one per tile of 16 segments -- wrnn_tile_wide_kernel: member 0 of the tile).
+struct Watch {
+    unsigned *progress;
+    int words, every;
+};
+bool watchable(Kind k) { return k == K_GENERIC || k == K_TILE || k == K_TILE_SPARSE || k == K_TILE_BF16 || k == K_TILE_WIDE; }
+// what a watched call may be: planned whole onto one of the five kernels.  `words` <- the words it writes.  w: NULL = only that (wrnn_watch_words)
+int watch_check(const wrnn_plan_traits *tr, int B, int T, const wrnn_options &o, const Watch *w, bool have_progress, int *words)
+{
+    wrnn_options whole = o;
+    whole.t_begin = 0; whole.t_end = 0;
+    Plan pl;
+    const int rc = make_plan(tr, B, T, &whole, &pl);
+    if (rc != WRNN_OK) return rc;
+    const char *const kn = KINDS[pl.kind].name;
+    if (!watchable(pl.kind)) {
+        set_err("a watched call runs on wrnn_generic_kernel, wrnn_tile_kernel, wrnn_tile_sparse_kernel, wrnn_tile_bf16_kernel or wrnn_tile_wide_kernel, the "
+                "kernels that are launched once for all steps: this call plans onto %s -- the resumable kernels stream through wrnn_options.t_begin / t_end "
+                "instead", kn);
+        return WRNN_ERR_ARG;
+    }
+    if (o.t_begin != 0 || (o.t_end != 0 && o.t_end != T)) {
+        set_err("a watched call runs whole: the step range [%d, %d) of T = %d is partial, and %s (planned) does not continue a call", o.t_begin, o.t_end, T, kn);
+        return WRNN_ERR_ARG;
+    }
+    const int need = pl.kind == K_GENERIC ? B : (B + SEG - 1) / SEG;
+    if (words) *words = need;
+    if (!w) return WRNN_OK;
+    if (!have_progress) { set_err("a watched call needs `progress`: it is NULL (planned: %s, %d words)", kn, need); return WRNN_ERR_ARG; }
+    if (w->every < 1) { set_err("progress_every = %d: a watched call publishes every progress_every >= 1 steps (planned: %s)", w->every, kn); return WRNN_ERR_ARG; }
+    if (w->words < need) {
+        set_err("progress_words = %d: %s publishes one word per workgroup that writes `out`, %d for %d segments (wrnn_watch_words)", w->words, kn, need, B);
+        return WRNN_ERR_ARG;
+    }
+    return WRNN_OK;
+}
 }  // namespace
 
 extern "C" size_t wrnn_workspace_bytes_segments(const wrnn_pack *p, int32_t n_segments, int32_t T, int32_t n_frames,
@@ -1070,10 +1108,11 @@ extern "C" size_t wrnn_workspace_bytes(const wrnn_pack *p, const wrnn_geometry *
     return wrnn_workspace_bytes_segments(p, g->B, g->T, g->n_frames, opt);
 }
 
-extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, const int32_t *seg_pos,
-                                      const int32_t *seg_lim, int32_t L, int32_t hop, int32_t n_frames,
-                                      const float *mels_up, const float *aux, const float *noise, float *out,
-                                      void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream_)
+// the one body of wrnn_generate_segments (watch == NULL) and wrnn_generate_segments_watched
+static int generate_segments(const wrnn_pack *p, int32_t B, int32_t T, const int32_t *seg_pos,
+                             const int32_t *seg_lim, int32_t L, int32_t hop, int32_t n_frames,
+                             const float *mels_up, const float *aux, const float *noise, float *out,
+                             void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream_, const Watch *watch)
 {
     const wrnn_options opts = norm_struct(opt), *o = &opts;
     const bool lib_noise = o->noise_lib == 1;       // (any other value but 0: make_plan refuses it)
@@ -1084,6 +1123,8 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     if (!p || !mels_up || !aux || (!noise && !lib_noise) || !out || !workspace) { set_err("NULL argument"); return WRNN_ERR_ARG; }
     int rc = check_segments(B, T, seg_pos, seg_lim, L, hop, n_frames);
     if (rc != WRNN_OK) return rc;
+    int watch_need = 0;     // a watched call: refused here, before anything is queued, unless it is planned whole onto a one-launch kernel
+    if (watch && (rc = watch_check(&p->tr, B, T, opts, watch, watch->progress != nullptr, &watch_need)) != WRNN_OK) return rc;
     Plan pl;      // (kernel, split and workspace layout do not depend on the step range: a continuation lands on the whole call's)
     if ((rc = make_plan(&p->tr, B, T, o, &pl)) != WRNN_OK) return rc;
     const KindDesc &k = KINDS[pl.kind];
@@ -1149,6 +1190,10 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
             g.noise = (const float *)(ws + l.nlib);
         }
         g.H = p->tr.gH; g.F = p->tr.gF; g.M = p->tr.gM; g.A = p->tr.gA; g.C = p->tr.C; g.B = B; g.T = T; g.hop = hop;
+        if (watch) {        // every word = 0 = "nothing yet", on the stream in front of the launch
+            HIPCHK(hipMemsetAsync(watch->progress, 0, (size_t)watch_need * sizeof(unsigned), stream));
+            g.progress = watch->progress; g.progress_every = watch->every;
+        }
         if ((rc = timer_mark(timer, stream)) != WRNN_OK) return rc;
         if (pl.kind == K_TILE_SPARSE && !p->ts_view) { set_err("this pack has no tile-sparse view"); return WRNN_ERR_ARG; }      // (the planner's traits are the pack's own: never)
         if (pl.kind == K_TILE_BF16 && !p->bf_bytes) { set_err("this pack has no bf16 view"); return WRNN_ERR_ARG; }             // (likewise)
@@ -1299,6 +1344,45 @@ extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, 
     }
     if (o->info) *o->info = info;
     return WRNN_OK;
+}
+
+extern "C" int wrnn_generate_segments(const wrnn_pack *p, int32_t B, int32_t T, const int32_t *seg_pos,
+                                      const int32_t *seg_lim, int32_t L, int32_t hop, int32_t n_frames,
+                                      const float *mels_up, const float *aux, const float *noise, float *out,
+                                      void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream_)
+{
+    return generate_segments(p, B, T, seg_pos, seg_lim, L, hop, n_frames, mels_up, aux, noise, out, workspace, workspace_bytes, opt, stream_, nullptr);
+}
+
+extern "C" int wrnn_generate_segments_watched(const wrnn_pack *p, int32_t B, int32_t T, const int32_t *seg_pos,
+                                              const int32_t *seg_lim, int32_t L, int32_t hop, int32_t n_frames,
+                                              const float *mels_up, const float *aux, const float *noise, float *out,
+                                              void *workspace, size_t workspace_bytes, const wrnn_options *opt, void *stream_,
+                                              unsigned *progress, int32_t progress_words, int32_t progress_every)
+{
+    const Watch w = {progress, progress_words, progress_every};
+    return generate_segments(p, B, T, seg_pos, seg_lim, L, hop, n_frames, mels_up, aux, noise, out, workspace, workspace_bytes, opt, stream_, &w);
+}
+
+extern "C" int wrnn_watch_words(const wrnn_pack *p, int32_t n_segments, int32_t T, const wrnn_options *opt, int32_t *words)
+{
+    if (!p || !words || n_segments < 1 || T < 1) { set_err("bad argument"); return WRNN_ERR_ARG; }
+    int need = 0;
+    const int rc = watch_check(&p->tr, n_segments, T, norm_struct(opt), nullptr, false, &need);
+    if (rc == WRNN_OK) *words = need;
+    return rc;
+}
+
+extern "C" int wrnn_debug_watch(const wrnn_plan_traits *traits, int32_t n_segments, int32_t T, const wrnn_options *opt, int32_t have_progress,
+                                int32_t progress_words, int32_t progress_every, int32_t *words)
+{
+    if (!traits || n_segments < 1 || T < 1) { set_err("bad argument"); return WRNN_ERR_ARG; }
+    const wrnn_plan_traits tr = norm_struct(traits);
+    const Watch w = {nullptr, progress_words, progress_every};
+    int need = 0;
+    const int rc = watch_check(&tr, n_segments, T, norm_struct(opt), have_progress < 0 ? nullptr : &w, have_progress > 0, &need);
+    if (rc == WRNN_OK && words) *words = need;
+    return rc;
 }
 
 extern "C" int wrnn_generate(const wrnn_pack *p, const wrnn_geometry *g, const float *mels_up, const float *aux,

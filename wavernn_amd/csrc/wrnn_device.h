@@ -147,7 +147,26 @@ struct GenArgs {
     float *out, *dbg_logits;            // [B][T], optional [T][B][C]
     const int *seg_pos, *seg_lim;       // [B]
     int H, F, M, A, C, B, T, hop;
+    unsigned *progress;                 // optional (wrnn_generate_segments_watched): one word per workgroup that writes `out`; NULL: nothing is published
+    int progress_every;                 // >= 1: a word is stored after every progress_every steps, and after the last
 };
+
+// A one-launch loop kernel says how far it has got: `word` <- done = "steps [0, done) of this workgroup's rows of `out` are complete and visible to a kernel
+// or copy launched from now on".  Called by the WHOLE workgroup behind the last barrier of step done - 1.  The producer form of a cross-CU hand-off: every
+// wave drains its own stores to `out`, the workgroup meets, ONE lane writes the XCD's L2 back (agent-scope release), waits for that write-back, and stores
+// the word, relaxed, at agent scope.  Nothing reads the word inside any kernel and the loop never waits for anybody: a host that stops looking changes
+// nothing.  The release costs microseconds, so the caller publishes once per progress_every steps, never per step.
+// tests/test_live_host.py runs this order against an observer at arbitrary times and shows the shortcuts that break it.
+__device__ __forceinline__ void publish_progress(unsigned *word, unsigned done, int tid)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(word, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
 
 // The tile-sparse view of one matrix of a generic pack (wrnn_tile_sparse.hip; built by tile_sparse_pack of wrnn_abi.hip).  A BLOCK ROW is 16 consecutive
 // rows (of one gate: the gates' row counts are multiples of 16), its list the columns in which any of the 16 values is non-zero, ascending, padded to whole

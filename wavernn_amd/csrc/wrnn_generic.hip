@@ -191,6 +191,10 @@ __global__ __launch_bounds__(GNT) void wrnn_generic_kernel(const GenArgs a)
             }
         }
         __syncthreads();
+        if (a.progress) {                               // (uniform) a watched call: this segment's word, once per progress_every steps and at the end
+            const int done = t + 1;
+            if (done % a.progress_every == 0 || done == T) publish_progress(a.progress + b, (unsigned)done, tid);
+        }
     }
 }
 

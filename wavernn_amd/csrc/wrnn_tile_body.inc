@@ -204,4 +204,8 @@
             }
         }
         __syncthreads();
+        if (a.progress) {                               // (uniform) a watched call: this tile's word, once per progress_every steps and at the end
+            const int done = t + 1;
+            if (done % a.progress_every == 0 || done == T) publish_progress(a.progress + blockIdx.x, (unsigned)done, tid);
+        }
     }

@@ -427,6 +427,10 @@ __global__ __launch_bounds__(TNT) void wrnn_tile_wide_kernel(const GenArgs a, co
             }
         }
         __syncthreads();
+        if (a.progress && m == 0) {                     // (uniform) a watched call: the tile's word, by the member that writes `out`
+            const int done = t + 1;
+            if (done % a.progress_every == 0 || done == T) publish_progress(a.progress + g, (unsigned)done, tid);
+        }
     }
 #undef WIDE_HANDOFF
 #undef WIDE_XS

@@ -14,8 +14,11 @@ LOOP_KEYS = dict(I_w='I.weight', I_b='I.bias', w_ih1='rnn1.weight_ih_l0', w_hh1=
                  fc2_w='fc2.weight', fc2_b='fc2.bias', fc3_w='fc3.weight', fc3_b='fc3.bias')
 
 
-#: loop kernels that keep their state between launches: a call can be continued in step slices (wrnn_options.t_begin / t_end)
+#: loop kernels that keep their state between launches: a call can be continued in step slices (wrnn_options.t_begin / t_end).  The other models stream
+#: through WATCHABLE_KERNELS: the call runs whole and says how far it has got (`run_segments(watch=...)`, `generate_unbatched(live=True)`)
 RESUMABLE_KERNELS = ('wrnn_loop_kernel', 'wrnn_duo_kernel', 'wrnn_sparse_kernel', 'wrnn_chain_kernel')
+#: loop kernels that are launched once for all steps and can publish their progress while they run (wrnn_generate_segments_watched)
+WATCHABLE_KERNELS = ('wrnn_generic_kernel', 'wrnn_tile_kernel', 'wrnn_tile_sparse_kernel', 'wrnn_tile_bf16_kernel', 'wrnn_tile_wide_kernel')
 #: ... and those that form the last up-sampling stage of the mel themselves (wrnn_options.mel_stage: they take `MelRows`)
 MEL_STAGE_KERNELS = ('wrnn_duo_kernel', 'wrnn_sparse_kernel', 'wrnn_chain_kernel')
 #: the persistent kernels: kernel -> (the algo that asks for it by name, what `auto` falls back to when its grid is refused -- cooperative launch not
@@ -197,9 +200,16 @@ class LoopEngine:
         o = self.options(**kw)
         return int(self.lib.wrnn_workspace_bytes_segments(self._pack, n_segments, T, n_frames, ctypes.byref(o)))
 
+    def watch_words(self, n_segments, T, algo='auto', clusters=0):
+        """`wrnn_watch_words`: the progress words a watched call over this many segments writes (one per workgroup that writes `out`); raises WrnnError
+        with the library's reason when the call would not run on one of WATCHABLE_KERNELS."""
+        o, words = self.options(algo, clusters=self._tile_clusters(algo, clusters, n_segments, T)), ctypes.c_int32(0)
+        _lib.check(self.lib.wrnn_watch_words(self._pack, n_segments, T, ctypes.byref(o), ctypes.byref(words)), 'wrnn_watch_words')
+        return int(words.value)
+
     def run_segments(self, mels_up, aux, seg_pos, seg_lim, T, noise, hop, algo='auto', force_x=None, want_logits=False,
                      check=True, depth=0, clusters=0, slab_steps=0, cond_valu=False, t_range=None, out=None, logits=None,
-                     phase_clocks=None, tuning=0, progress=None, sparse_groups=0, noise_seed=0, noise_seg_id=None, _fallback=False):
+                     phase_clocks=None, tuning=0, progress=None, sparse_groups=0, noise_seed=0, noise_seg_id=None, watch=None, _fallback=False):
         """mels_up (L,feat) / aux (n_frames,4*aux_dims) / noise: float32 CUDA tensors; seg_pos / seg_lim: host
         int32 arrays (B,) -- segment b, step t reads position seg_pos[b]+t, zero conditioning from seg_lim[b] on
         (several utterances: concatenated conditioning).  Returns out (B,T) CUDA [and logits (T,B,C)].
@@ -214,7 +224,11 @@ class LoopEngine:
         conditioning slab (wrnn_options.progress; must not touch the device).
         noise=None: the library draws the noise itself (wrnn_options.noise_lib), slab by slab on the stream, from the counter-based generator
         keyed by `noise_seed`; noise_seg_id: one 64-bit stream id per segment (None: segment b has id b).  The samples are those of the same
-        call fed `rng.library_noise(...)`; a continued call (t_range) needs nothing but the same seed and ids."""
+        call fed `rng.library_noise(...)`; a continued call (t_range) needs nothing but the same seed and ids.
+        watch=(words, every): a WATCHED call (`wrnn_generate_segments_watched`; a kernel of WATCHABLE_KERNELS, whole calls only -- anything else raises):
+        `words` is a uint32 (or int32) CUDA tensor of at least `watch_words(...)` elements that the caller has zeroed on this stream; after every `every`
+        steps each workgroup that writes `out` stores the steps it has finished into its word, so min(words[:watch_words]) = the columns of `out` that a
+        kernel or copy launched from then on may read.  Same samples as the plain call."""
         rows_in = mels_up if isinstance(mels_up, MelRows) else None
         if rows_in is not None:
             mels_up = rows_in.rows
@@ -280,9 +294,16 @@ class LoopEngine:
             o.mel_stage, o.mel_rows, o.mel_scale = 1, int(mels_up.shape[0]), rows_in.scale
             o.mel_taps, o.seg_moff = rows_in.taps.ctypes.data, seg_moff.ctypes.data
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.wrnn_generate_segments(self._pack, B, T, seg_pos.ctypes.data, seg_lim.ctypes.data, L, hop, n_frames,
-                                             mels_up.data_ptr(), aux.data_ptr(), None if lib_noise else noise.data_ptr(), out.data_ptr(),
-                                             self._ws.data_ptr(), self._ws.numel(), ctypes.byref(o), stream)
+        call_args = (self._pack, B, T, seg_pos.ctypes.data, seg_lim.ctypes.data, L, hop, n_frames,
+                     mels_up.data_ptr(), aux.data_ptr(), None if lib_noise else noise.data_ptr(), out.data_ptr(),
+                     self._ws.data_ptr(), self._ws.numel(), ctypes.byref(o), stream)
+        if watch is None:
+            rc = self.lib.wrnn_generate_segments(*call_args)
+        else:
+            words, every = watch
+            if not (words.is_cuda and words.dtype in (torch.uint32, torch.int32) and words.is_contiguous()):
+                raise ValueError('watch: (a contiguous uint32 CUDA tensor, steps between two publications)')
+            rc = self.lib.wrnn_generate_segments_watched(*call_args, words.data_ptr(), int(words.numel()), int(every))
         if rc == _lib.ERR_RESIDENCY and algo == 'tile' and clusters > 1 and not named_clusters:
             # the W workgroups of a tile are not co-resident right now: plain wrnn_tile_kernel needs no residency (the same samples), from now on
             self._warn_tile('cooperative launch refused (' + self.lib.wrnn_last_error().decode() + ')')
@@ -291,7 +312,7 @@ class LoopEngine:
                 self._progress_keep.pop()
             return self.run_segments(mels_up if rows_in is None else rows_in, aux, seg_pos, seg_lim, T, noise, hop, algo=algo, force_x=force_x,
                                      want_logits=want_logits, check=check, slab_steps=slab_steps, cond_valu=cond_valu, t_range=t_range, out=out, logits=logits,
-                                     phase_clocks=phase_clocks, tuning=tuning, progress=progress, noise_seed=noise_seed, noise_seg_id=noise_seg_id)
+                                     phase_clocks=phase_clocks, tuning=tuning, progress=progress, noise_seed=noise_seed, noise_seg_id=noise_seg_id, watch=watch)
         if rc == _lib.ERR_RESIDENCY and t0 == 0 and (algo == 'auto' or _fallback):
             # the persistent grid is not co-resident right now (CU masking, a smaller partition, another cooperative kernel).  `auto`
             # degrades step by step (FALLBACK_ALGO): wrnn_sparse_kernel -> two workgroups per CU (wrnn_duo_kernel) -> one (wrnn_loop_kernel;
@@ -329,7 +350,7 @@ class LoopEngine:
             # ... the same refusal on the first slice of a step-sliced run (only the loop kernels continue a call): the caller, who owns
             # the slicing and the noise stream, redoes the whole call on the stream kernel
             raise _lib.ResidencyError('cooperative launch refused (' + why + ')')
-        _lib.check(rc, 'wrnn_generate_segments')
+        _lib.check(rc, 'wrnn_generate_segments' if watch is None else 'wrnn_generate_segments_watched')
         self._launches = (self._launches if t0 > 0 else 0) + int(self._info.launches)
         if t0 == 0:
             self._slice_algo = KERNEL_ALGOS.get((self._info.kernel or b'').decode(), (None, None))[0]

@@ -68,9 +68,14 @@ def main(argv=None):
                          "'tile_bf16' is 'tile' with the weights rounded to bfloat16 on the bf16 matrix pipe -- not the reference's arithmetic")
     ap.add_argument('--unbatched', '-u', action='store_true', help='no folds: every utterance one unfolded segment, up to 64 per loop call (single process)')
     ap.add_argument('--chunk-steps', type=int, default=None, help='--unbatched: finish and copy out the audio in slices of K loop steps while the loop goes on')
+    ap.add_argument('--live', action='store_true', help='--unbatched --chunk-steps K on a loop kernel that is launched once for all steps (models of non-shipped dims): the call '
+                        'runs whole, publishes its progress, and the chunks leave while it runs (generate_unbatched(live=True)).  No effect without --chunk-steps, nor on the '
+                        'shipped dims this tool builds its model with: their kernels continue a call and stream in step slices anyway')
     a = ap.parse_args(argv)
     if a.noise in ('cpu', 'library') and a.seed is None:
         ap.error(f'--noise {a.noise} needs --seed')
+    if a.live and not a.unbatched:
+        ap.error('--live needs --unbatched')
     if a.chunk_steps is not None and not a.unbatched:
         ap.error('--chunk-steps needs --unbatched')
     if a.chunk_steps is not None and a.chunk_steps < 1:
@@ -100,7 +105,7 @@ def main(argv=None):
     seeds = [a.seed + u for u in range(len(mels))] if a.seed is not None else None
     noise = a.noise or ('cpu' if seeds is not None else 'device')
     if a.unbatched:
-        outs = generate_unbatched(model, [m.to(dev) for m in mels], True, seeds, noise_source=noise, chunk_steps=a.chunk_steps)
+        outs = generate_unbatched(model, [m.to(dev) for m in mels], True, seeds, noise_source=noise, chunk_steps=a.chunk_steps, live=a.live)
     else:
         outs = generate_corpus(model, [m.to(dev) for m in mels], a.target, a.overlap, True, seeds, group=group, noise_source=noise, finish='own')
     out_dir = Path(a.output)

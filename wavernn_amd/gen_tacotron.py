@@ -44,10 +44,14 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=None, help='decode up to N (1..8) sentences per Tacotron kernel and vocode them in one pass (--unbatched: unfolded, generate_unbatched)')
     ap.add_argument('--groups', type=int, default=1, choices=[1, 2], help='--batch: decoder groups per launch (2: a group on each half of a 256-CU device)')
     ap.add_argument('--seed', type=int, default=0, help='--batch: sentence i draws its sampling noise under seed + i')
+    ap.add_argument('--live', action='store_true', help='--batch N --unbatched: passed on to generate_unbatched(live=True).  No effect here: this tool asks for no chunks '
+                        '(every sentence is written when the pass has ended), and the shipped dims it builds its vocoder with run on kernels that continue a call')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if a.batch is not None and not 1 <= a.batch <= 8:
         ap.error('--batch: 1..8 sentences per decoder kernel')
+    if a.live and (a.batch is None or a.batched):
+        ap.error('--live needs --batch N --unbatched')
     if a.groups != 1 and a.batch is None:
         ap.error('--groups needs --batch')
     return a
@@ -83,7 +87,7 @@ def main(argv=None):
         if a.batched:
             wavs = generate_corpus(voc, mels, a.target, a.overlap, True, seeds=seeds, noise_source='library')
         else:
-            wavs = generate_unbatched(voc, mels, True, seeds=seeds, noise_source='library')
+            wavs = generate_unbatched(voc, mels, True, seeds=seeds, noise_source='library', live=a.live)
         t2 = time.perf_counter()
         for name, wav, (_, lin, _) in zip(names, wavs, outs):
             save_wav(np.asarray(wav), out_dir / name, voc.sample_rate)

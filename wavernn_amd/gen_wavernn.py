@@ -19,7 +19,7 @@ from .model import WaveRNN
 from .synthetic import SHIPPED
 
 
-def gen_from_file(model, load_path: Path, save_path: Path, batched, target, overlap, mu_law=True, stream_steps=None):
+def gen_from_file(model, load_path: Path, save_path: Path, batched, target, overlap, mu_law=True, stream_steps=None, live=False):
     """gen_wavernn.py:38-65 for a `.npy` mel."""
     suffix = load_path.suffix
     if suffix == '.wav':
@@ -44,7 +44,7 @@ def gen_from_file(model, load_path: Path, save_path: Path, batched, target, over
         import time
         from .dsp import save_wav
         t0, chunks, first = time.perf_counter(), [], None
-        for c in model.generate_stream(mel, mu_law, chunk_steps=stream_steps):
+        for c in model.generate_stream(mel, mu_law, chunk_steps=stream_steps, live=live):
             first = first if first is not None else time.perf_counter() - t0
             chunks.append(c)
         out = np.concatenate(chunks)
@@ -79,6 +79,9 @@ def main(argv=None):
                          "'tile_bf16' is 'tile' with the weights rounded to bfloat16 on the bf16 matrix pipe -- not the reference's arithmetic")
     ap.add_argument('--stream', action='store_true', help='--unbatched: hand the audio on in chunks while the loop goes on (WaveRNN.generate_stream); prints the time to the first chunk')
     ap.add_argument('--chunk-steps', type=int, default=2200, help='--stream: loop steps per chunk')
+    ap.add_argument('--live', action='store_true', help='--stream on a loop kernel that is launched once for all steps (models of non-shipped dims; --algo tile*): '
+                        'the call runs whole, publishes its progress, and the chunks leave while it runs (generate_stream(live=True)).  No effect without --stream, '
+                        'nor on the shipped dims this tool builds its model with: their kernels continue a call and stream in step slices anyway')
     ap.set_defaults(batched=True)
     a = ap.parse_args(argv)
     if a.stream and a.batched:
@@ -99,7 +102,7 @@ def main(argv=None):
         torch.manual_seed(a.seed)
         model.noise_seed = a.seed
     out, path = gen_from_file(model, Path(a.file).expanduser().resolve(), Path(a.output), a.batched, a.target, a.overlap,
-                              stream_steps=a.chunk_steps if a.stream else None)
+                              stream_steps=a.chunk_steps if a.stream else None, live=a.live)
     n = out.shape[0]
     print(f'{path}: {n} samples ({n / model.sample_rate:.2f} s), loop {model.last_loop_kernel} {model.last_loop_ms:.1f} ms '
           f'= {n / model.last_loop_ms:.1f} kHz')

@@ -390,19 +390,21 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def generate_stream(self, mels, mu_law, chunk_steps=2200, dtype=np.float64):
+    def generate_stream(self, mels, mu_law, chunk_steps=2200, dtype=np.float64, live=False):
         """`generate(mels, path, False, ., ., mu_law)` -- ONE utterance, unbatched -- as a Python generator of waveform chunks: the loop runs in slices of
         `chunk_steps` steps, each finished by `wrnn_post_chunk` and copied out while the next slice runs (`batch.unbatched_chunks`), so the first
         chunk_steps / sample_rate seconds of audio arrive after one slice instead of after the whole utterance.  The arrays (`dtype`, each the caller's
         own) concatenate to exactly what `generate` returns under the same `noise_source`: 'cpu' consumes torch's global generator as `generate` does
         (constructor draws included), 'library' draws under `noise_seed` / `noise_key`.  Nothing is written to disk; the training flag is restored when
-        the generator is exhausted or closed.  A loop kernel that does not continue a call yields the utterance as one chunk (one warning)."""
+        the generator is exhausted or closed.  A loop kernel that does not continue a call yields the utterance as one chunk (one warning) -- unless
+        live=True and it is one of `engine.WATCHABLE_KERNELS` (every model of non-shipped dims): the call then runs whole, publishes its progress, and
+        a side stream finishes and copies out every chunk it has passed (`batch.generate_unbatched`); the same chunks, the same bits."""
         from .batch import unbatched_chunks
         self._require_hip_device(next(self.parameters()).device)
         if self.mode not in ('RAW', 'MOL'):
             raise RuntimeError("Unknown model mode value - ", self.mode)
         for _, _, samples in unbatched_chunks(self, [mels], mu_law, seeds=[self.noise_seed], noise_source=self.noise_source, chunk_steps=chunk_steps,
-                                              max_utterances=1, dtype=dtype, global_rng=True):
+                                              max_utterances=1, dtype=dtype, global_rng=True, live=live):
             yield samples
 
     def _run_sliced(self, eng, mels_up, aux, B, T, stride, chunk, algo, device, sparse_groups=0):

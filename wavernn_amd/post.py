@@ -99,6 +99,14 @@ def chunk_host_tables(hop, n_classes, mu_law):
     return np.linspace(1, 0, 20 * hop), (_fold.decode_mu_law(y32.astype(np.float64), n_classes, False) if mu_law else None)
 
 
+def chunk_tables_on_device(hop, n_classes, mu_law, device):
+    """Make the cached tables `chunk_on_device` reads (tail fade, mu-law expansion) on the CURRENT stream: for a caller whose first launch would
+    otherwise create them on a side stream."""
+    _fade_tables(0, hop, device)
+    if mu_law:
+        _mu_law_lut(n_classes, device)
+
+
 def chunk_on_device(segments, wave_len, t0, t1, hop, n_classes, mu_law, out64=None, out32=None, row=None, min_wave_len=None):
     """One `wrnn_post_chunk` launch on the current stream: steps [t0, t1) of the post-loop stage of unfolded utterances.  segments: float32 CUDA
     (rows, T), the loop's `out`, of which only [t0, t1) need be finished; wave_len: int32 CUDA (n,); row: int32 CUDA (n,) or None (utterance u is
